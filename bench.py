@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the GritLM embedding-encode hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 without a launcher: bench.py starts its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N > 1 without a launcher: bench.py starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,13 +12,19 @@ starts.  N > 1: one replica per GPU, every rank encodes its own 256-doc batch (d
 no data-path collective, weak scaling); value = docs of all ranks / max-over-ranks time.
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline:     dominant kernel (gemm_bf16_nt, bf16 MFMA bound) measured live with HIP events,
+  roofline:     dominant kernel (gemm_bf16_nt, bf16 MFMA bound) measured live with HIP events during the timed steps.
+A plain run stops there: set up, warm up, time K steps, write the outputs (--dump-outputs), print the line.
+--dump-outputs DIR: the pooled, normalised embeddings of the last timed step as DIR/embeddings.npy (float32, DOCS x hidden; rank r > 0
+                writes DIR/embeddings_rank<r>.npy).  Weights and token ids are seeded, so the same arguments give the same inputs every run.
+--full adds everything else (each leg can still be dropped with its --no-* flag):
+  gemm_over_vendor_*: hipBLASLt on the same GEMM shapes in the same process,
+  ragged_batch: padded vs packed path on a ragged batch,
   parity_full_depth: the engine's embeddings of the timed batch vs the reference-equivalent module in FP32 on this GPU on the engine's own
                 weights (numeric bounds, both precision policies), + the fixture model against the fp32 numpy oracle,
   cpu_baseline: the reference's CPU encode (stock transformers.MistralModel + bidirectional mask + pooling, bit-equal to the reference
                 on the reference-generated fixtures; oracle/torch_reference.py) timed on this host's cores on a bounded sample (N = 1 only),
   rocm_torch_baseline: the same Python on this GPU through stock PyTorch-ROCm (bf16, sdpa) at the full config -- what a user gets today,
-  contrastive:  BASELINE configs[2] as stated (256 pairs x (1 + 8) x 512 tokens per GPU, GradCache chunk 32), 3 timed steps,
+  contrastive:  BASELINE configs[2] as stated (256 pairs x (1 + 8) x 512 tokens per GPU, GradCache chunk 32), 1 timed step (--contrastive-steps),
   mixtral_8x7b_seq2048 / rag_doc_caching: BASELINE configs[3] / configs[4] as time-boxed child processes (N = 1 only; --no-mixtral / --no-rag).
 """
 import argparse
@@ -767,19 +773,23 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--layers", type=int, default=32, help="debug only; anything but 32 marks the line invalid")
+    ap.add_argument("--full", action="store_true", help="also run every comparator, baseline, parity and secondary leg (the --no-* flags "
+                    "below select among them); without it only the headline steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the embeddings of the last timed step to DIR/embeddings.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-contrastive", action="store_true", help="skip the contrastive pairs/s leg")
     ap.add_argument("--no-ragged", action="store_true", help="skip the ragged-batch (padded vs packed) leg")
     ap.add_argument("--pairs", type=int, default=256, help="contrastive pairs per GPU per step (BASELINE configs[2]: 256)")
     ap.add_argument("--chunk", type=int, default=32, help="GradCache chunk size (BASELINE configs[2]: 32)")
-    ap.add_argument("--contrastive-steps", type=int, default=3, help="timed contrastive steps (after one warm-up step); ~52 s each at configs[2]")
+    ap.add_argument("--contrastive-steps", type=int, default=1, help="timed contrastive steps (after one warm-up step); ~52 s each at configs[2] "
+                    "(1 keeps --full within ten minutes; earlier lines used 3)")
     ap.add_argument("--pass1-precision", default="f16_stream", choices=("bf16", "f16_stream", "f16_operands"),
                     help="precision policy of GradCache pass 1 in the contrastive leg (the pass that defines the loss); default: the policy that "
                          "meets the north-star's |loss - fp32 loss| < 1e-3 at depth 32")
     ap.add_argument("--contrastive-parity-pairs", type=int, default=16, help="pairs of the timed batch re-run through the fp32 reference "
                     "(forward + backward) for the contrastive leg's parity object; 0 = skip")
-    ap.add_argument("--contrastive-parity-loss-pairs", type=int, default=256, help="pairs for the forward-only loss datum of that object "
-                    "(default 256 = the whole per-GPU batch of configs[2]: ~2.5 minutes of fp32 reference; 64: ~40 s)")
+    ap.add_argument("--contrastive-parity-loss-pairs", type=int, default=64, help="pairs for the forward-only loss datum of that object "
+                    "(default 64: ~40 s of fp32 reference, keeps --full within ten minutes; 256 = the whole per-GPU batch of configs[2], ~2.5 minutes)")
     ap.add_argument("--no-torch-baseline", action="store_true", help="skip the stock PyTorch-ROCm encode on this GPU")
     ap.add_argument("--no-mixtral", action="store_true", help="skip the BASELINE configs[3] leg (Mixtral-8x7B shape, 64 x seq2048)")
     ap.add_argument("--no-rag", action="store_true", help="skip the BASELINE configs[4] leg (512 passages x seq2048 with KV + 128 new tokens)")
@@ -788,6 +798,8 @@ def main():
                          "the line is marked INVALID (tests/test_bench_cli.py)")
     args = ap.parse_args()
     dry = args.dry_cpu
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     forced = bool(os.environ.get("GRIT_BENCH_FORCE_DIST"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not forced:
@@ -877,10 +889,15 @@ def main():
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt_max = float(t.item())
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "embeddings.npy" if rank == 0 else f"embeddings_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), emb.float().cpu().numpy())
 
     # ---- ragged batch (SURVEY §8d "C2 padded variant"): lengths ~ U{64..512}, right-padded; padded vs packed (un-padded) path
     ragged = None
-    if not args.no_ragged and not dry:
+    if args.full and not args.no_ragged and not dry:
         g2 = torch.Generator(device=dev).manual_seed(99 + rank)
         lens = torch.randint(64, SEQ + 1, (DOCS,), generator=g2, device=dev)
         lens[0] = SEQ
@@ -902,7 +919,7 @@ def main():
                   "docs_per_s_padded_path": dps_pad, "docs_per_s_packed_path": dps_pack,
                   "bit_identical": bool(torch.equal(e_pad, e_pack))}
 
-    baselines = not multi and not dry and not args.no_torch_baseline
+    baselines = args.full and not multi and not dry and not args.no_torch_baseline
     hf_sd = eng.to_hf_state_dict() if baselines else None           # views of the engine's weights: the stock module is loaded from them
     emb_engine = emb.float().clone()
     if not dry:
@@ -981,7 +998,8 @@ def main():
     # collective until the RCCL watchdog aborts the job and the primary line would be lost: a deadline thread on every rank prints the
     # primary line (with the leg marked as timed out) and exits the process cleanly instead.
     guard, emitted = None, []
-    if multi and not args.no_contrastive:
+    run_contrastive = args.full and not args.no_contrastive
+    if multi and run_contrastive:
         def _late_line():
             if rank != 0 or emitted:
                 return None
@@ -992,7 +1010,7 @@ def main():
             return json.dumps(line)
         guard = deadline_guard(float(os.environ.get("GRIT_BENCH_CONTRASTIVE_DEADLINE_S", "900")), _late_line, emit)
     contrastive = None
-    if not args.no_contrastive:
+    if run_contrastive:
         try:
             if dry:
                 contrastive = dry_contrastive_leg(eng, world, rank, dist, pairs=args.pairs, group=2, chunk=args.chunk, seq=SEQ)
@@ -1032,7 +1050,7 @@ def main():
             line["collectives"] = {"backend": dist.get_backend(), "library": "gloo (dry run)" if dry else
                                    "RCCL (torch.distributed 'nccl' backend on ROCm)",
                                    "ranks": dist.get_world_size(), "encode_data_path_collectives": 0}
-        if not multi and not dry and not args.no_cpu_baseline:
+        if args.full and not multi and not dry and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             try:
                 fixture_datum, line["cpu_baseline_numpy_oracle"] = full_depth_parity(dev)
@@ -1061,7 +1079,7 @@ def main():
                                          "docs_per_s_over_default": (cands[best].get("docs_per_s") or 0.0) / docs_per_s,
                                          "all": {k: {"max_one_minus_cos": v.get("max_one_minus_cos"), "docs_per_s": v.get("docs_per_s"),
                                                      "docs_per_s_over_default": (v.get("docs_per_s") or 0.0) / docs_per_s} for k, v in cands.items()}}
-        if not multi and not dry:
+        if args.full and not multi and not dry:
             import gc as _gc
             _gc.collect()
             torch.cuda.empty_cache()

@@ -17,7 +17,7 @@ def _run(*flags):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                              "GRIT_BENCH_FORCE_DIST", "GRIT_DIST_WORLD1")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-cpu", "--layers", "1", "--steps", "2", "--warmup", "1",
-                        "--pairs", "4", "--chunk", "2", *flags], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--pairs", "4", "--chunk", "2", "--full", *flags], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]      # ONE line on stdout: library chatter (gloo, RCCL) goes to stderr
@@ -43,6 +43,38 @@ def test_single_process_dry_run_has_no_collectives():
     assert "starting" not in r.stderr
     assert line["n_gpus"] == 1 and "collectives" not in line and "INVALID" in line
     assert "error" not in line["contrastive"]
+
+
+def _run_plain(*flags):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GRIT_BENCH_FORCE_DIST")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-cpu", "--layers", "1", *flags], capture_output=True, text=True,
+                       timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_the_headline_only():
+    """Without --full the line holds the headline and nothing that needs a run of its own."""
+    line = _run_plain("--steps", "3", "--warmup", "1")
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert "contrastive" not in line and "ragged_batch" not in line and "INVALID" in line
+
+
+def test_dump_outputs_writes_the_same_embeddings_every_run(tmp_path):
+    import numpy as np
+    outs = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        _run_plain("--steps", "2", "--warmup", "1", "--dump-outputs", str(d))
+        assert sorted(os.listdir(d)) == ["embeddings.npy"]
+        outs.append(np.load(d / "embeddings.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (8, 64) and np.isfinite(outs[0]).all()
+    np.testing.assert_array_equal(outs[0], outs[1])
+    np.testing.assert_allclose(np.linalg.norm(outs[0], axis=1), 1.0, rtol=1e-5)
 
 
 def test_under_a_launcher_environment_bench_does_not_relaunch():

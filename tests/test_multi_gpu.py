@@ -290,7 +290,7 @@ def test_in_process_encode_across_two_real_devices_is_bit_identical(tmp_path):
 @two_gpus
 def test_bench_two_gpus_prints_one_json_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--layers", "2", "--pairs", "8",
-                        "--chunk", "4", "--contrastive-steps", "1", "--no-ragged"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--chunk", "4", "--contrastive-steps", "1", "--no-ragged", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
     d = json.loads(lines[0])
