@@ -58,14 +58,19 @@ __global__ void __launch_bounds__(256) moe_router_top2_k(const uint16_t* __restr
     float p[E], den = 0.f;
 #pragma unroll
     for (int e = 0; e < E; ++e) { p[e] = expf(acc[e] - mx); den += p[e]; }
-    int e0 = 0, e1 = -1;
+    int e0 = 0, e1 = 1;
     float p0 = -1.f, p1 = -1.f;
 #pragma unroll
-    for (int e = 0; e < E; ++e) {                    // descending, lowest index first on ties (torch.topk on equal values)
+    for (int e = 0; e < E; ++e) {                    // descending, lowest index first on ties (the oracle's stable argsort)
       const float pe = p[e] / den;
       if (pe > p0) { p1 = p0; e1 = e0; p0 = pe; e0 = e; }
       else if (pe > p1) { p1 = pe; e1 = e; }
     }
+    // a non-finite softmax (a NaN or +inf logit, or every logit -inf: den is NaN) makes every compare above false; such a row takes
+    // experts (0, 1) at (0.5, 0.5) -- the oracle's stable argsort puts NaN last -- so that no consumer ever sees an index outside [0, E).
+    // Finite rows: den is in [1, E] and the selection above is untouched.
+    const bool nonfinite = !__builtin_isfinite(den);
+    if (nonfinite) { e0 = 0; e1 = 1; p0 = 0.5f; p1 = 0.5f; }
     if (lane == 0) {
       const float s = p0 + p1;
       experts[2 * t] = e0; experts[2 * t + 1] = e1;
@@ -82,7 +87,8 @@ __global__ void __launch_bounds__(256) moe_router_top2_k(const uint16_t* __restr
 template <int E>
 __global__ void __launch_bounds__(256) moe_router_top2_f32_k(const float* __restrict__ h, const uint16_t* __restrict__ ln_w, float eps,
                                                              const uint16_t* __restrict__ gate_w, int64_t T, int H,
-                                                             int32_t* __restrict__ experts, float* __restrict__ weights) {
+                                                             int32_t* __restrict__ experts, float* __restrict__ weights,
+                                                             unsigned int* __restrict__ ovf) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint2* gw = reinterpret_cast<uint2*>(smem);                   // [E][H/4] : 4 bf16 per entry
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -123,18 +129,24 @@ __global__ void __launch_bounds__(256) moe_router_top2_f32_k(const float* __rest
     float p[E], den = 0.f;
 #pragma unroll
     for (int e = 0; e < E; ++e) { p[e] = expf(acc[e] - mx); den += p[e]; }
-    int e0 = 0, e1 = -1;
+    int e0 = 0, e1 = 1;
     float p0 = -1.f, p1 = -1.f;
 #pragma unroll
-    for (int e = 0; e < E; ++e) {                    // descending, lowest index first on ties (torch.topk on equal values)
+    for (int e = 0; e < E; ++e) {                    // descending, lowest index first on ties (the oracle's stable argsort)
       const float pe = p[e] / den;
       if (pe > p0) { p1 = p0; e1 = e0; p0 = pe; e0 = e; }
       else if (pe > p1) { p1 = pe; e1 = e; }
     }
+    // a non-finite softmax (a NaN or +inf logit, or every logit -inf: den is NaN) makes every compare above false; such a row takes
+    // experts (0, 1) at (0.5, 0.5) -- the oracle's stable argsort puts NaN last -- so that no consumer ever sees an index outside [0, E).
+    // Finite rows: den is in [1, E] and the selection above is untouched.
+    const bool nonfinite = !__builtin_isfinite(den);
+    if (nonfinite) { e0 = 0; e1 = 1; p0 = 0.5f; p1 = 0.5f; }
     if (lane == 0) {
       const float s = p0 + p1;
       experts[2 * t] = e0; experts[2 * t + 1] = e1;
       weights[2 * t] = p0 / s; weights[2 * t + 1] = p1 / s;
+      if (nonfinite) atomicOr(ovf, 1u);            // the policy's overflow reached the router: report it even if no fp16 store saw it
     }
   }
 }
@@ -289,7 +301,10 @@ __global__ void __launch_bounds__(IDX_T) moe_hist_k(const int32_t* __restrict__ 
   const int64_t base = (int64_t)blockIdx.x * IDX_CHUNK;
   for (int j = tid; j < IDX_CHUNK; j += IDX_T) {
     const int64_t i = base + j;
-    if (i < n) atomicAdd(&h[experts[i]], 1);
+    if (i < n) {
+      const int e = experts[i];
+      if (e >= 0 && e < E) atomicAdd(&h[e], 1);       // an entry outside [0, E) is not counted (the routers never write one)
+    }
   }
   __syncthreads();
   if (tid < E) chunk_counts[(int64_t)blockIdx.x * E + tid] = h[tid];
@@ -324,7 +339,8 @@ __global__ void __launch_bounds__(IDX_T) moe_rank_k(const int32_t* __restrict__ 
   const int64_t base = (int64_t)blockIdx.x * IDX_CHUNK;
   for (int r = 0; r < IDX_CHUNK / IDX_T; ++r) {
     const int64_t i = base + r * IDX_T + tid;
-    const int e = i < n ? experts[i] : -1;
+    int e = i < n ? experts[i] : -1;
+    if (e >= E) e = -1;                               // outside [0, E): no row (moe_hist_k did not count it either)
     int my_rank = 0;
     for (int k = 0; k < E; ++k) {
       const uint64_t m = __ballot(e == k);
@@ -494,6 +510,8 @@ extern "C" int grit_moe_router_top2_f32(const float* h, const void* ln_w, float 
   GRIT_REQUIRE(E == 4 || E == 8 || E == 16, GRIT_E_UNSUPPORTED, "grit_moe_router_top2_f32: num_experts=%d (4, 8 and 16 are built)", E);
   GRIT_REQUIRE((size_t)(E + 1) * H * 2 <= 160 * 1024, GRIT_E_UNSUPPORTED, "grit_moe_router_top2_f32: gate [%d,%d] + norm weight exceed LDS", E, H);
   GRIT_REQUIRE(aligned16(h) && aligned16(gate_w) && aligned16(ln_w), GRIT_E_BADARG, "grit_moe_router_top2_f32: pointers must be 16-byte aligned");
+  unsigned int* ovf = f16_flag_ptr();
+  GRIT_REQUIRE(ovf != nullptr, GRIT_E_LAUNCH, "grit_moe_router_top2_f32: the overflow flag word of this device is not reachable");
   const size_t lds = (size_t)(E + 1) * H * 2;
   int64_t nb = (T + 3) / 4;
   if (nb > 2048) nb = 2048;
@@ -503,7 +521,7 @@ extern "C" int grit_moe_router_top2_f32(const float* h, const void* ln_w, float 
     static std::atomic<uint64_t> optin_{0};                                                                                   \
     lds_optin_once(moe_router_top2_f32_k<E_>, optin_, 160 * 1024);                                                            \
     hipLaunchKernelGGL(moe_router_top2_f32_k<E_>, dim3((unsigned)nb), dim3(256), lds, st, h, (const uint16_t*)ln_w, eps,      \
-                       (const uint16_t*)gate_w, T, H, experts, weights);                                                      \
+                       (const uint16_t*)gate_w, T, H, experts, weights, ovf);                                                 \
   } while (0)
   if (E == 4) GRIT_ROUTER32(4); else if (E == 8) GRIT_ROUTER32(8); else GRIT_ROUTER32(16);
   GRIT_CHECK_LAUNCH("grit_moe_router_top2_f32");

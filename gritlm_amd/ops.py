@@ -636,7 +636,8 @@ def gemv(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None, epil
 
 def gemv_expert(x: torch.Tensor, w_stack: torch.Tensor, expert: torch.Tensor, out: torch.Tensor | None = None, epilogue: int = EPI_STORE) -> torch.Tensor:
     """x [B,K] @ w_stack[expert[0]]^T for a stack [E,N,K]: the expert index is read on the DEVICE (``expert``: an int32 tensor or view whose
-    first element is the index), so a sparse-MoE decode step can be captured in a graph.  STORE / SWIGLU; fp16 stack: the fp16 formats."""
+    first element is the index), so a sparse-MoE decode step can be captured in a graph; the kernel clamps the index to [0, E).  STORE / SWIGLU;
+    fp16 stack: the fp16 formats."""
     B, K = x.shape
     E, N, _ = w_stack.shape
     f16 = w_stack.dtype == F16
@@ -648,7 +649,7 @@ def gemv_expert(x: torch.Tensor, w_stack: torch.Tensor, expert: torch.Tensor, ou
         raise TypeError("gemv_expert: expert must be an int32 CUDA tensor")
     fn = _lib.load().grit_gemv_f16_expert if f16 else _lib.load().grit_gemv_bf16_expert
     check(fn(_chk2d(x, F16 if f16 else BF16, "x"), _chk3d(w_stack, F16 if f16 else BF16, "w_stack"), _chk2d(out, odt, "out"), expert.data_ptr(),
-             w_stack.stride(0), B, N, K, x.stride(0), w_stack.stride(1), out.stride(0), epilogue, _stream()), "grit_gemv_expert")
+             w_stack.stride(0), E, B, N, K, x.stride(0), w_stack.stride(1), out.stride(0), epilogue, _stream()), "grit_gemv_expert")
     return out
 
 

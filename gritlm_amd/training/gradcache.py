@@ -18,7 +18,9 @@ from typing import Dict, List
 import torch
 import torch.distributed as dist
 
+from .. import ops
 from .._lib import GritHipError
+from ..encoder import F16_POLICIES
 
 
 def dist_active() -> bool:
@@ -262,8 +264,39 @@ class GradCacheStep:
             self.profile.update(out)
         return dict(self.profile or {})
 
+    def _read_f16_flag(self, clear: bool = True) -> bool:
+        """This device's fp16 overflow flag (read, then cleared): set when a kernel of the fp16 no-grad forward stored an inf / nan."""
+        return ops.f16_overflow_flag(self.model.train_engine.device, clear)
+
+    def _check_pass1_overflow(self, cross: bool) -> None:
+        """Raise on EVERY rank, before the loss or any gradient is touched, if pass 1 overflowed the fp16 range on any rank (the
+        policies' contract: raise, never saturate silently).  With cross-device negatives the ranks agree over the process group: one
+        MAX all-reduce of one int, issued on every rank whenever the policy is fp16, so the collective sequence is the same everywhere."""
+        if self.precision not in F16_POLICIES:
+            return
+        local = bool(self._read_f16_flag())
+        where = f"device {getattr(getattr(self.model, 'train_engine', None), 'device', 'cpu')}" if local else ""
+        if cross and dist_active():
+            rank = dist.get_rank()
+            t = torch.tensor([rank + 1 if local else 0], dtype=torch.int64,
+                             device="cuda" if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            first = int(t.item()) - 1
+            if first >= 0 and not local:
+                where = f"rank {first}'s device"
+            elif local:
+                where += f" (rank {rank})"
+        if where:
+            raise GritHipError(f"GradCache pass 1 under precision='{self.precision}': an activation exceeded the fp16 range on {where}; "
+                               "the representations and the loss of this step are invalid and no gradient was computed -- use 'bf16'")
+
     def __call__(self, query: Dict, passage: Dict, sync: bool = True) -> torch.Tensor:
         model = self.model
+        eng = getattr(model, "train_engine", None)
+        if eng is not None:
+            self.precision = eng.nograd_precision              # (set_nograd_precision() between steps takes effect)
+        if self.precision in F16_POLICIES:
+            self._read_f16_flag()          # clear: a flag left over from earlier work must not be blamed on this step
         q_chunks, p_chunks = split_inputs(query, self.chunk_size), split_inputs(passage, self.chunk_size)
         loss_fn = model.emb_loss_fn
         cross = bool(getattr(loss_fn, "negatives_cross_device", False))
@@ -292,6 +325,8 @@ class GradCacheStep:
                 if cross and (gq if which == "q" else gp) is not None:
                     (gq if which == "q" else gp).flush()         # the tower's remainder goes out before the next tower starts
         q_reps, p_reps = torch.cat(q_list, dim=0), torch.cat(p_list, dim=0)
+        if not cross:
+            self._check_pass1_overflow(False)
         self.last_reps = (q_reps, p_reps)          # (pass 1's representations: parity probes read them)
         # loss + representation-gradient cache
         q_leaf, p_leaf = q_reps.detach().requires_grad_(), p_reps.detach().requires_grad_()
@@ -299,6 +334,7 @@ class GradCacheStep:
         if cross:
             with _Span(self.profile, "exposed_gather_ms", gpu):
                 q_all, p_all = gq.finish(), gp.finish()
+            self._check_pass1_overflow(True)       # after the gathers: every rank has issued the same collectives up to here
             if self.profile is not None:
                 self.profile["gather_collectives"] = gq.calls + gp.calls
                 self.profile["gather_bytes_received"] = (q_all.numel() + p_all.numel()) * q_all.element_size() * (gq.world - 1) // gq.world

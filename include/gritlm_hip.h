@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 5
+#define GRIT_ABI_VERSION 6
 
 enum {
   GRIT_OK = 0,
@@ -460,13 +460,14 @@ int grit_attn_decode_rope_f16(const void* qkv, const float* cos_tab, const float
 int grit_argmax_advance_f32(const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history,
                             int64_t hist_stride, int32_t* step, int B, void* stream);
 
-/* Sparse-MoE decode (ABI 5; MixtralSparseMoeBlock.forward, scripts/modeling_mixtral_gritlm.py:839-882, at 1..8 rows): x [B,K] times ONE
- * matrix of the stack W [E,N,K] -- matrix expert[0], an int32 in DEVICE memory (the router's choice for the row, so that the decode step
- * stays one HIP graph); w_expert_stride = elements between consecutive matrices.  Epilogues STORE and SWIGLU; formats of grit_gemv_bf16 /
- * grit_gemv_f16 (f16 STORE writes fp32). */
-int grit_gemv_bf16_expert(const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride, int B, int N, int K,
+/* Sparse-MoE decode (ABI 5; E since ABI 6; MixtralSparseMoeBlock.forward, scripts/modeling_mixtral_gritlm.py:839-882, at 1..8 rows): x [B,K]
+ * times ONE matrix of the stack W [E,N,K] -- matrix expert[0], an int32 in DEVICE memory (the router's choice for the row, so that the decode
+ * step stays one HIP graph); w_expert_stride = elements between consecutive matrices, E >= 1 the number of matrices: the kernel clamps
+ * expert[0] to [0, E), so no index value reads outside the stack.  Epilogues STORE and SWIGLU; formats of grit_gemv_bf16 / grit_gemv_f16
+ * (f16 STORE writes fp32). */
+int grit_gemv_bf16_expert(const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride, int E, int B, int N, int K,
                           int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream);
-int grit_gemv_f16_expert(const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride, int B, int N, int K,
+int grit_gemv_f16_expert(const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride, int E, int B, int N, int K,
                          int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream);
 /* ... and its combine on fp16 operands (:876-880 in fp32): h[b] += weights[b,0] y[2b] + weights[b,1] y[2b+1] (h [B,H] the fp32 residual stream,
  * y [2B,H] the chosen experts' fp32 outputs), h16 = fp16(h) (the operand copy the next norm + GEMV reads; beyond the range: the overflow flag). */

@@ -2952,17 +2952,30 @@ def check_native_generate_f16(cfg_name="tiny", P=21, new=10, rows=2, policy="f16
     dec2 = MistralDecoder(eng2, torch.from_numpy(lm))
     (eng2.layers[0].w13 if cfg.get("num_local_experts") else eng2.layers[0].wgu).mul_(400.0)       # |gate|, |up| x 400: silu(g) u beyond 65504 for some elements
     fell = raised = False
+    states = []
+    make_state = dec2._state
+    dec2._state = lambda *a, **kw: states.append(make_state(*a, **kw)) or states[-1]            # (the decode state of each call, read below)
     try:
         dec2.generate(torch.from_numpy(prompt[:1]).to(DEV), 3, past_key_values=[(k[:, :, :0], v[:, :, :0]) for k, v in kv])
     except GritHipError:
         raised = True
+    experts_valid = True
+    if cfg.get("num_local_experts"):
+        # the overflowing layer's inf reaches the next layer's router as a NaN row: its choice must still be two valid, distinct experts
+        # (the expert GEMVs index the weight stack with it)
+        experts_valid = len(states) == 1 and _experts_valid(states[0]["experts"].cpu().numpy(), cfg["num_local_experts"])
+    dec2._state = make_state
     t_fb = dec2.generate(torch.from_numpy(prompt[:1]).to(DEV), 3, past_key_values=[(k[:, :, :0], v[:, :, :0]) for k, v in kv], on_overflow="bf16")
     fell = dec2.last_precision == "bf16 (f16 overflow)" and t_fb.shape == (1, 3)
-    ok &= raised and fell
+    eng2.set_precision("bf16")                                   # the fallback's tokens == a plain bf16 decode of the same weights
+    t_plain = dec2.generate(torch.from_numpy(prompt[:1]).to(DEV), 3, past_key_values=[(k[:, :, :0], v[:, :, :0]) for k, v in kv])
+    fallback_equal = dec2.last_precision == "bf16" and bool(torch.equal(t_fb, t_plain))
+    ok &= raised and fell and experts_valid and fallback_equal
     return _res(f"native decode on fp16 operands [{cfg_name}, {policy}] vs fp32 oracle: 1-cos of the logits", bool(ok), f16_doc=f["doc"], bf16_doc=b["doc"],
                 f16_prompt_on_decode_path=f["prompt_on_decode_path"], f16_doc_from_bf16_cache=f["doc_bf16_cache"],
                 f16_prompt_prefill=f["prompt_prefill"], f16_logit_abs_err=f["doc_abs"], bf16_logit_abs_err=b["doc_abs"], logit_std=f["std"],
-                clear_frac=f["clear_frac"], overflow_raised=raised, overflow_fell_back=fell)
+                clear_frac=f["clear_frac"], overflow_raised=raised, overflow_fell_back=fell, overflow_experts_valid=experts_valid,
+                fallback_equals_bf16_decode=fallback_equal)
 
 
 def check_native_generate_prompt_chunk(cfg_name="gqa", B=2, P=11, new=5, policy="bf16"):
@@ -3986,6 +3999,441 @@ def check_get_cache_f16():
     return _res("encode(get_cache=True) under the fp16 policies", bool(ok), **out)
 
 
+# ---------------------------------------------------------------------------------------------
+# Routing edges and the fp16 policies' overflow contract on the sparse-MoE and GradCache paths.  Every router output is read back to the
+# host and checked for 0 <= e < E, e0 != e1 BEFORE anything consumes it.
+def _experts_valid(sel: np.ndarray, E: int) -> bool:
+    return bool(((sel >= 0) & (sel < E)).all() and (sel[:, 0] != sel[:, 1]).all())
+
+
+def _index_exact(sel: np.ndarray, E: int, counts, row_token, rows) -> bool:
+    """counts / row_token / rows of grit_moe_index == np.bincount / stable argsort / its inverse, and rows is a permutation of [0, 2T)."""
+    flat = sel.reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    inv = np.empty_like(order); inv[order] = np.arange(order.size)
+    r = rows.cpu().numpy().reshape(-1)
+    return (np.array_equal(counts.cpu().numpy(), np.bincount(flat, minlength=E)) and np.array_equal(row_token.cpu().numpy(), (order // 2).astype(np.int32))
+            and np.array_equal(r, inv.astype(np.int32)) and np.array_equal(np.sort(r), np.arange(flat.size, dtype=np.int32)))
+
+
+def _router_edge_logits(E: int) -> tuple:
+    """Constructed logit rows [n, E] of small integers (exact in bf16 and in every summation order) where the lowest-index rule decides:
+    exact ties of 1st / 2nd, of 2nd / 3rd, a triple tie, all-equal; every other logit is at least 1 below (clearly separated)."""
+    rng = np.random.default_rng(300 + E)
+    rows, kinds = [], []
+    base = lambda: -rng.permutation(E).astype(np.float32) - 2.0                  # distinct, all <= -2
+    for i, j in ((0, 1), (0, E - 1), (E - 2, E - 1), (1, E // 2), (E // 2, 1)):
+        L = base(); L[i] = L[j] = 3.0; rows.append(L); kinds.append("tie12")
+    for i, j, k in ((E - 1, 0, 1), (0, E - 2, E - 1), (E // 2, 1, E - 1), (1, 0, E - 1)):
+        L = base(); L[i] = 5.0; L[j] = L[k] = 3.0; rows.append(L); kinds.append("tie23")
+    for t in ((1, 2, 3), (E - 3, E - 2, E - 1)):
+        L = base(); L[list(t)] = 3.0; rows.append(L); kinds.append("tie3")
+    rows.append(np.zeros(E, np.float32)); kinds.append("all_equal")
+    return np.stack(rows), kinds
+
+
+def check_moe_router_edges(E=8, H=256, eps=1e-5):
+    """Both routers (bf16 grit_moe_router_top2, fp32-stream grit_moe_router_top2_f32), both entry points (moe_route* with the index,
+    moe_router_top2 without) on CONSTRUCTED rows, no `clear` mask: exact ties (1st / 2nd, 2nd / 3rd, triple; two identical gate rows),
+    all-equal logits, softmax underflow (every probability but one exactly 0: the 2nd pick is decided by index, its weight is exactly 0),
+    and non-finite rows (+inf, NaN, all -inf logits).  Selections == the oracle's lowest-index rule on every row; weights within the existing
+    tolerances; non-finite rows -> experts (0, 1) at (0.5, 0.5); the fp32 router sets the overflow flag exactly when a non-finite row is
+    present.  Recorded, not asserted: whether torch.topk on the device picks the same index on the exact-tie rows."""
+    assert H > E + 1
+    det, ok = {}, True
+    L, kinds = _router_edge_logits(E)
+    n_fin = L.shape[0]
+    # gate: one-hot rows (logit e = x[:, e] exactly) + a shared column E of ones (a -inf there makes EVERY logit -inf)
+    gate = np.zeros((E, H), np.float32); gate[np.arange(E), np.arange(E)] = 1.0; gate[:, E] = 1.0
+    # --- bf16 router rows: the designed logits, underflow, non-finite
+    X = np.zeros((n_fin, H), np.float32); X[:, :E] = L
+    under = []
+    for i in (0, E - 1, E // 2):
+        r = np.zeros(H, np.float32); r[i] = 120.0; under.append(r); kinds.append("underflow")   # exp(-120) == 0 in fp32
+    r = np.zeros(H, np.float32); r[E - 1] = 120.0; r[1] = 60.0; under.append(r); kinds.append("underflow_2nd_tiny")
+    X = np.concatenate([X, np.stack(under)])
+    nonfin = []
+    r = np.zeros(H, np.float32); r[2] = np.inf; nonfin.append(r)
+    r = np.zeros(H, np.float32); r[E - 1] = np.nan; nonfin.append(r)
+    r = np.zeros(H, np.float32); r[E] = -np.inf; nonfin.append(r)
+    kinds_nf = ["pos_inf", "nan", "all_neg_inf"]
+    X = np.concatenate([X, np.stack(nonfin)]); kinds = kinds + kinds_nf
+    T = X.shape[0]
+    tie = np.array([k.startswith("tie") or k == "all_equal" for k in kinds])
+    nf = np.array([k in kinds_nf for k in kinds])
+    und = np.array([k == "underflow" for k in kinds])
+    with np.errstate(invalid="ignore", over="ignore"):
+        w_ref, sel_ref, logits = O.moe_router(X, gate, 2, emulate_bf16=True)
+    sel_ref = sel_ref.astype(np.int32)
+    ok &= bool((sel_ref[nf] == np.array([0, 1])).all())                           # (the oracle's stable argsort: NaN last)
+    xb = bf(X)
+    topk_same = {}
+    for kind, run in (("bf16", None), ("f32", None)):
+        if kind == "bf16":
+            xin, gw, lnw = xb, bf(gate), None
+        else:
+            # fp32 stream h with the norm folded in: logits = s * h[e] / rms(h); ln_w = 1, gate one-hot x s (s = 16: rms-normalised rows reach
+            # logits of s * sqrt(H) = 256, so a single non-zero entry underflows every other probability)
+            s = 16.0
+            gw = bf(gate * np.where(np.arange(H) < E, s, 1.0)[None, :].astype(np.float32))
+            lnw = bf(np.ones(H, np.float32))
+            Xf = X.copy(); Xf[und | (np.array(kinds) == "underflow_2nd_tiny")] = 0.0
+            for t in np.nonzero(und)[0]:
+                Xf[t, int(np.argmax(X[t]))] = 1.0
+            # (an fp32 stream row holding 120 and 60 is normalised to logits 229 / 114: both underflow; the f32 router gets a third
+            #  underflow row instead)
+            t2 = kinds.index("underflow_2nd_tiny"); Xf[t2, E - 1] = 1.0
+            xin = torch.from_numpy(Xf).to(DEV)
+            h64 = Xf.astype(np.float64)
+            with np.errstate(invalid="ignore", over="ignore"):
+                xn = h64 / np.sqrt(np.mean(h64 ** 2, axis=1, keepdims=True) + eps)
+                lg = xn @ f32(gw).astype(np.float64).T
+                pr = np.exp(lg - lg.max(1, keepdims=True)); pr /= pr.sum(1, keepdims=True)
+            sref = np.argsort(-pr, axis=1, kind="stable")[:, :2].astype(np.int32)
+            wref = np.take_along_axis(pr, sref, axis=1); wref = wref / wref.sum(1, keepdims=True)
+            wtol = 2e-6 + 2.5e-7 * float(np.nanmax(np.abs(np.where(np.isfinite(lg), lg, 0.0))))
+        if kind == "bf16":
+            sref, wref, wtol, lg = sel_ref, w_ref.astype(np.float64), 2.0 ** -7, logits.astype(np.float64)
+        # entry without the index: caller-owned buffers pre-filled with garbage, so a row the kernel did not write is caught
+        ex = torch.full((T, 2), -7, dtype=torch.int32, device=DEV)
+        wt = torch.full((T, 2), -3.0, dtype=torch.float32, device=DEV)
+        finite_rows = ~nf
+        if kind == "f32":
+            _f16_flag()
+            ops.moe_router_top2(xin[torch.from_numpy(np.nonzero(finite_rows)[0]).to(DEV)].contiguous(), gw,
+                                ex[:int(finite_rows.sum())], wt[:int(finite_rows.sum())], ln_w=lnw, eps=eps)
+            det["f32_flag_finite_rows"] = _f16_flag(); ok &= not det["f32_flag_finite_rows"]
+            for j, t in enumerate(np.nonzero(nf)[0]):
+                one = torch.empty((1, 2), dtype=torch.int32, device=DEV); onew = torch.empty((1, 2), dtype=torch.float32, device=DEV)
+                ops.moe_router_top2(xin[int(t):int(t) + 1].contiguous(), gw, one, onew, ln_w=lnw, eps=eps)
+                det[f"f32_flag_{kinds[t]}"] = _f16_flag(); ok &= det[f"f32_flag_{kinds[t]}"]
+            ex.fill_(-7); wt.fill_(-3.0)
+            ops.moe_router_top2(xin, gw, ex, wt, ln_w=lnw, eps=eps)
+            det["f32_flag_all_rows"] = _f16_flag(); ok &= det["f32_flag_all_rows"]
+        else:
+            ops.moe_router_top2(xin, gw, ex, wt)
+        sel, w = ex.cpu().numpy(), wt.cpu().numpy().astype(np.float64)
+        valid = _experts_valid(sel, E)
+        det[f"{kind}_valid"] = valid; ok &= valid
+        if not valid:
+            continue                                                               # nothing below may consume invalid indices
+        det[f"{kind}_sel_equal"] = bool(np.array_equal(sel, sref)); ok &= det[f"{kind}_sel_equal"]
+        werr = float(np.max(np.abs(w - wref)[~nf]))
+        det[f"{kind}_max_weight_err"] = werr; ok &= werr <= wtol
+        det[f"{kind}_nonfinite_rows"] = bool((sel[nf] == np.array([0, 1])).all() and (w[nf] == 0.5).all()); ok &= det[f"{kind}_nonfinite_rows"]
+        und_rows = und if kind == "bf16" else (und | (np.array(kinds) == "underflow_2nd_tiny"))
+        det[f"{kind}_underflow_w2_zero"] = bool((w[und_rows, 1] == 0.0).all() and (w[und_rows, 0] == 1.0).all())
+        ok &= det[f"{kind}_underflow_w2_zero"]
+        # entry with the index: the same bits, and the index exact on them
+        if kind == "bf16":
+            e2, w2, counts, row_token, rows = ops.moe_route(xin, gw)
+        else:
+            e2, w2, counts, row_token, rows = ops.moe_route_f32(xin, lnw, eps, gw)
+        s2 = e2.cpu().numpy()
+        same = _experts_valid(s2, E) and np.array_equal(s2, sel) and bool(torch.equal(w2, wt))
+        det[f"{kind}_route_same_bits"] = same; ok &= same
+        if same:
+            det[f"{kind}_index_exact"] = _index_exact(s2, E, counts, row_token, rows); ok &= det[f"{kind}_index_exact"]
+        if kind == "f32":
+            _f16_flag()
+        # torch.topk on the device, on the exact-tie rows (recorded: the bf16 parity checks rest on the lowest-index rule)
+        probs = torch.softmax(torch.from_numpy(lg[tie]).to(DEV, torch.float32), dim=1)
+        topk_same[kind] = float((probs.topk(2, dim=1).indices.cpu().numpy() == sref[tie]).all(1).mean())
+        det[f"{kind}_torch_topk_tie_agreement"] = topk_same[kind]
+    # two IDENTICAL gate rows with random x: bit-equal logits whatever the summation order; rows where the tied pair leads clearly
+    rng = np.random.default_rng(77 + E)
+    a, b = 1, E - 2
+    g2 = O.bf16_round(rng.standard_normal((E, H)).astype(np.float32) * 0.01)
+    g2[a] = g2[b] = O.bf16_round(rng.standard_normal(H).astype(np.float32) * 0.5)
+    x2 = O.bf16_round(rng.standard_normal((256, H)).astype(np.float32))
+    lg2 = x2.astype(np.float64) @ g2.astype(np.float64).T
+    x2 = x2 * np.sign(lg2[:, a:a + 1]).astype(np.float32)                           # the tied pair's logit > 0 on every row
+    lg2 = x2.astype(np.float64) @ g2.astype(np.float64).T
+    others = np.delete(lg2, [a, b], axis=1).max(1)
+    keep = lg2[:, a] - others > 1.0                                                 # >> bf16 rounding of a logit of a few units
+    x2 = x2[keep]
+    ex = torch.full((x2.shape[0], 2), -7, dtype=torch.int32, device=DEV); wt = torch.empty((x2.shape[0], 2), dtype=torch.float32, device=DEV)
+    ops.moe_router_top2(bf(x2), bf(g2), ex, wt)
+    sel = ex.cpu().numpy()
+    _, sref2, _ = O.moe_router(x2, g2, 2, emulate_bf16=True)
+    det["identical_gate_rows"] = int(keep.sum())
+    same = _experts_valid(sel, E) and bool((sel == np.array([a, b])).all()) and np.array_equal(sel, sref2) and bool((wt == 0.5).all())
+    det["identical_gate_rows_sel_equal"] = same; ok &= same and keep.sum() >= 64
+    return _res(f"moe router edges [E={E},H={H}]: ties / all-equal / underflow / non-finite, both routers, both entries", bool(ok), **det)
+
+
+def _moe_index(experts: torch.Tensor, E: int):
+    """grit_moe_index on a caller-made experts [T, 2] array; outputs pre-filled with -1."""
+    from gritlm_amd import _lib
+    lib = _lib.load()
+    T = experts.shape[0]
+    counts = torch.full((E,), -1, dtype=torch.int32, device=DEV)
+    row_token = torch.full((2 * T,), -1, dtype=torch.int32, device=DEV)
+    rows = torch.full((T, 2), -1, dtype=torch.int32, device=DEV)
+    ws = torch.empty((int(lib.grit_moe_index_workspace_ints(T, E)),), dtype=torch.int32, device=DEV)
+    _lib.check(lib.grit_moe_index(experts.data_ptr(), T, E, counts.data_ptr(), row_token.data_ptr(), rows.data_ptr(), ws.data_ptr(), ops._stream()),
+               "grit_moe_index")
+    return counts, row_token, rows
+
+
+def check_moe_index_multichunk(Ts=(2047, 2048, 2049, 6145, 32771), Es=(2, 8, 16)):
+    """grit_moe_index across its 4096-entry chunks: 2T just under, at and just over one chunk, several chunks with a partial last one, and
+    17 chunks; everything on one expert, one expert empty, alternating, random skewed.  counts / row_token / rows == np.bincount / stable
+    argsort / its inverse exactly, rows a permutation of [0, 2T)."""
+    rng = np.random.default_rng(404)
+    det, ok = {}, True
+    for T in Ts:
+        for E in Es:
+            n = 2 * T
+            p = 0.5 ** np.arange(E); p /= p.sum()
+            dists = {"one": np.full(n, E - 1), "one_empty": np.arange(n) % (E - 1) + (np.arange(n) % (E - 1) >= E // 2),
+                     "alternating": np.arange(n) % E, "skewed": rng.choice(E, size=n, p=p)}
+            for name, flat in dists.items():
+                sel = flat.astype(np.int32).reshape(T, 2)
+                counts, row_token, rows = _moe_index(torch.from_numpy(sel).to(DEV), E)
+                good = _index_exact(sel, E, counts, row_token, rows)
+                if name == "one_empty":
+                    good &= int(np.bincount(flat, minlength=E)[E // 2]) == 0 if E > 2 else True
+                ok &= good
+                if not good:
+                    det[f"T{T}_E{E}_{name}"] = False
+    det["cases"] = len(Ts) * len(Es) * 4
+    return _res("moe index across chunks (T = 2047 .. 32771, E = 2 / 8 / 16): exact counting sort", bool(ok), **det)
+
+
+def check_gemv_expert_index_clamped(E=5, N=1024, K=512, big=False):
+    """ABI 6: grit_gemv_{bf16,f16}_expert clamp the device-read index to [0, E).  An index of -1 (and INT_MIN) == the slice-0 GEMV, an
+    index of E (and INT_MAX) == the slice-(E-1) GEMV, bit for bit, both formats, STORE and SWIGLU, 1 and 3 rows; ``big``: the 8x7B w13
+    stack's strides."""
+    from gritlm_amd import _lib
+    v = int(_lib.load().grit_version())
+    if v < 6:
+        return _res("gemv_expert index clamp", False, abi=v)
+    if big:
+        E, N, K = 8, 28672, 4096
+    ok, det = True, {}
+    g = torch.Generator(device=DEV).manual_seed(19)
+    stack_bf = (torch.randn((E, N, K), generator=g, device=DEV) * 0.05).to(torch.bfloat16)
+    idx = torch.tensor([-1, -2 ** 31, E, 2 ** 31 - 1], dtype=torch.int32, device=DEV)
+    want_slice = (0, 0, E - 1, E - 1)
+    for dt in (torch.bfloat16, torch.float16):
+        stack = stack_bf if dt == torch.bfloat16 else stack_bf.to(torch.float16)
+        for B in (1, 3):
+            x = torch.randn((B, K), generator=g, device=DEV).to(dt)
+            for epi in (EPI_STORE, EPI_SWIGLU):
+                refs = {e: ops.gemv(x, stack[e], epilogue=epi) for e in (0, E - 1)}
+                for k in range(idx.numel()):
+                    got = ops.gemv_expert(x, stack, idx[k:k + 1], epilogue=epi)
+                    same = bool(torch.equal(got, refs[want_slice[k]]))
+                    ok &= same
+                    det[f"{str(dt)[6:]}_B{B}_epi{epi}_idx{int(idx[k])}"] = same
+        del stack
+    del stack_bf
+    return _res(f"gemv_expert[E={E},N={N},K={K}]: out-of-range indices clamp to the first / last slice (bit for bit)", bool(ok),
+                abi=v, all_equal=all(det.values()), cases=len(det))
+
+
+def _spy_ops(names, epilogues):
+    """Wrap gritlm_amd.ops functions (the engines call them through the module): record max |out| of every call whose epilogue is in
+    ``epilogues`` and every experts array a router returned.  Returns (record dict, restore function)."""
+    rec = {"act_max": 0.0, "experts": []}
+    orig = {n: getattr(ops, n) for n in names}
+
+    def wrap(n, fn):
+        def f(*a, **kw):
+            r = fn(*a, **kw)
+            if n.startswith("moe_route"):
+                rec["experts"].append(r[0].cpu().numpy())
+                return r
+            grouped = n.startswith("gemm_nt_grouped")
+            epi = a[4] if n == "gemm_nt_grouped_epi" else kw.get("epilogue")
+            if epi in epilogues:
+                o = kw.get("out")
+                o = o if o is not None else (r if isinstance(r, torch.Tensor) else None)
+                if o is not None:
+                    rows = int(a[3]) if grouped else int(a[0].shape[0])       # (the rows this call wrote, not a larger workspace)
+                    rec["act_max"] = max(rec["act_max"], float(o[:rows].float().abs().max()))
+            return r
+        return f
+    for n in names:
+        setattr(ops, n, wrap(n, orig[n]))
+    return rec, lambda: [setattr(ops, n, f) for n, f in orig.items()]
+
+
+def _mixtral_w13_scaled(cfg_name, seed, scale=400.0):
+    """make_weights with layer 0's experts' w1 / w3 x ``scale`` (the decode check's construction: silu(g) u beyond 65504 for some
+    elements, so under f16_operands layer 0's expert output is inf and layer 1 routes a NaN row)."""
+    cfg = synth.CONFIGS[cfg_name]
+    w = synth.make_weights(cfg, seed)
+    for e in range(cfg["num_local_experts"]):
+        for n in ("w1", "w3"):
+            k = f"layers.0.block_sparse_moe.experts.{e}.{n}.weight"
+            w[k] = O.bf16_round(w[k] * scale)
+    return cfg, w
+
+
+def check_mixtral_f16_overflow_encode(cfg_name="moe-tiny"):
+    """Sparse-MoE encode under f16_operands when layer 0's fp16 expert output overflows (w13 x 400; the bf16-policy activation magnitude is
+    recorded): every router output valid; the encoder engine raises from check_f16_overflow (padded and packed); GritLM(precision=
+    'f16_operands') raises and names the device, the same model under 'bf16' afterwards returns finite rows (no stale flag);
+    GritLM(precision='auto') returns, stands on 'bf16' and stays, rows bit-equal to a precision='bf16' model's; the training engine's
+    no-grad f16 forward on the same weights raises from check_f16_overflow()."""
+    import tempfile
+    from gritlm_amd import GritLM
+    from gritlm_amd._lib import GritHipError
+    from gritlm_amd.training import GritLMTrainModel
+    cfg, w = _mixtral_w13_scaled(cfg_name, 6)
+    E = cfg["num_local_experts"]
+    sd = {k: torch.from_numpy(v) for k, v in w.items()}
+    ids, mask = synth.make_batch(cfg, 4, 60, seed=33, min_len=9)
+    tid, tm = torch.from_numpy(ids).to(DEV), torch.from_numpy(mask).to(DEV)
+    det, ok = {}, True
+    rec, restore = _spy_ops(("gemm_nt_grouped", "moe_route", "moe_route_f32"), (EPI_SWIGLU,))
+    try:
+        eb = MistralEncoderEngine.from_state_dict(EncoderConfig.from_dict(cfg), sd, DEV)
+        ef = MistralEncoderEngine.from_state_dict(EncoderConfig.from_dict(cfg), sd, DEV).set_precision("f16_operands")
+        for packed in (False, True):
+            rec["act_max"] = 0.0
+            rb = eb.encode_pooled(tid, tm, "mean", True, packed=packed)
+            det[f"bf16_act_max_packed={packed}"] = rec["act_max"]
+            ok &= bool(torch.isfinite(rb).all()) and rec["act_max"] > 65504.0
+            _f16_flag()
+            rec["experts"].clear()
+            ef.encode_pooled(tid, tm, "mean", True, packed=packed)
+            valid = all(_experts_valid(s, E) for s in rec["experts"]) and len(rec["experts"]) >= cfg["num_hidden_layers"]
+            det[f"f16_router_outputs_valid_packed={packed}"] = valid; ok &= valid
+            try:
+                ef.check_f16_overflow(); det[f"engine_raises_packed={packed}"] = False
+            except GritHipError as ex:
+                det[f"engine_raises_packed={packed}"] = "fp16 range" in str(ex)
+            ok &= det[f"engine_raises_packed={packed}"] is True
+        sents = [" ".join(synth.WORDS[(5 * i + j) % len(synth.WORDS)] for j in range(12 + 4 * i)) for i in range(5)]
+        with tempfile.TemporaryDirectory() as td:
+            d16 = synth.build_mixtral_dir(os.path.join(td, "x16"), cfg_name, 6, "bfloat16", weights=w)
+            kw = dict(pooling_method="mean", attn="bbcc", device="cuda:0", torch_dtype=torch.bfloat16)
+            e_b = GritLM(d16, precision="bf16", **kw).encode(sents, batch_size=4, max_length=64)
+            ok &= bool(np.isfinite(e_b).all())
+            mx = GritLM(d16, precision="f16_operands", **kw)
+            try:
+                mx.encode(sents, batch_size=4, max_length=64); det["explicit_raises"] = False
+            except GritHipError as ex:
+                det["explicit_raises"] = "fp16 range" in str(ex) and "cuda:0" in str(ex)
+            ok &= det["explicit_raises"] is True
+            mx.set_precision("bf16")
+            e_after = mx.encode(sents, batch_size=4, max_length=64)
+            det["bf16_after_raise_equal"] = bool(np.array_equal(e_after, e_b)); ok &= det["bf16_after_raise_equal"]
+            del mx
+            ma = GritLM(d16, precision="auto", **kw)
+            e_a = ma.encode(sents, batch_size=4, max_length=64)
+            det["auto_rung"] = ma.precision
+            e_a2 = ma.encode(sents, batch_size=4, max_length=64)
+            det["auto_bit_equal_bf16"] = bool(np.array_equal(e_a, e_b) and np.array_equal(e_a2, e_b))
+            ok &= det["auto_rung"] == "bf16" and ma.precision == "bf16" and det["auto_bit_equal_bf16"]
+            del ma
+            m = GritLMTrainModel(model_name_or_path=d16, mode="embedding", pooling_method="mean", normalized=True, attn="bbcc",
+                                 temperature=0.02, negatives_cross_device=False, device="cuda", torch_dtype=torch.bfloat16)
+            m.enable_native()
+            m.train_engine.set_nograd_precision("f16_operands")
+            for packed in (False, True):
+                m.native_packed = packed
+                _f16_flag()
+                rec["experts"].clear()
+                with torch.no_grad():
+                    m.encode({"input_ids": tid, "attention_mask": tm})
+                valid = all(_experts_valid(s, E) for s in rec["experts"]) and len(rec["experts"]) > 0
+                det[f"train_router_outputs_valid_packed={packed}"] = valid; ok &= valid
+                try:
+                    m.train_engine.check_f16_overflow(); det[f"train_nograd_raises_packed={packed}"] = False
+                except GritHipError as ex:
+                    det[f"train_nograd_raises_packed={packed}"] = "fp16 range" in str(ex)
+                ok &= det[f"train_nograd_raises_packed={packed}"] is True
+            del m
+    finally:
+        restore()
+        torch.cuda.empty_cache()
+    return _res(f"mixtral f16_operands overflow on encode [{cfg_name}]: raises / steps down, valid routing", bool(ok), **det)
+
+
+def check_gradcache_f16_overflow(cfg_name="gqa", policies=("f16_operands", "f16_stream"), scale=300.0):
+    """GradCacheStep with an fp16 pass 1 whose activations overflow (dense: gate / up x ``scale``, SwiGLU beyond 65504 -- recorded;
+    sparse-MoE: layer 0's w13 x 400): the step raises GritHipError before the loss backward / pass 2 -- every parameter bit-identical,
+    no .grad written; after set_nograd_precision('bf16') the same step object runs, its loss finite and equal to a fresh bf16 step's.
+    A stale flag (set by an overflowing fp16 GEMM before the step) is not blamed on a tame fp16 step."""
+    import tempfile
+    from gritlm_amd._lib import EPI_SWIGLU_STACKED, GritHipError
+    from gritlm_amd.training import GradCacheStep, GritLMTrainModel
+    moe = bool(synth.CONFIGS[cfg_name].get("num_local_experts"))
+    det, ok = {}, True
+    if moe:
+        cfg, w = _mixtral_w13_scaled(cfg_name, 3)
+    else:
+        cfg = synth.CONFIGS[cfg_name]
+        w = synth.make_weights(cfg, 3)
+        for k in list(w):
+            if "gate_proj" in k or "up_proj" in k:
+                w[k] = O.bf16_round(w[k] * scale)
+    qi, qm = synth.make_batch(cfg, 2, 24, seed=41, min_len=6)
+    pi, pm = synth.make_batch(cfg, 4, 40, seed=42, min_len=9)
+    q = {"input_ids": torch.from_numpy(qi).to(DEV), "attention_mask": torch.from_numpy(qm).to(DEV)}
+    p = {"input_ids": torch.from_numpy(pi).to(DEV), "attention_mask": torch.from_numpy(pm).to(DEV)}
+    with tempfile.TemporaryDirectory() as td:
+        build = synth.build_mixtral_dir if moe else synth.build_mistral_dir
+        dh = build(os.path.join(td, "hot"), cfg_name, 3, "bfloat16", weights=w)
+        dt = build(os.path.join(td, "tame"), cfg_name, 3, "bfloat16")
+
+        def model(d):
+            m = GritLMTrainModel(model_name_or_path=d, mode="embedding", pooling_method="mean", normalized=True, attn="bbcc",
+                                 temperature=0.02, negatives_cross_device=False, device="cuda", torch_dtype=torch.bfloat16)
+            m.enable_native()
+            return m
+        fresh = model(dh)
+        rec, restore = _spy_ops(("gemm_nt", "gemm_nt_grouped", "gemm_nt_grouped_epi"), (EPI_SWIGLU, EPI_SWIGLU_STACKED))
+        try:
+            with torch.no_grad():
+                fresh.encode(dict(q)); fresh.encode(dict(p))
+        finally:
+            restore()
+        det["bf16_swiglu_act_max"] = rec["act_max"]
+        ok &= rec["act_max"] > 65504.0
+        ref_loss = float(GradCacheStep(fresh, chunk_size=2, precision="bf16")(dict(q), dict(p)).item())
+        ok &= bool(np.isfinite(ref_loss))
+        del fresh
+        for pol in (policies if not moe else ("f16_operands",)):
+            m = model(dh)
+            params = {n: t.detach().clone() for n, t in m.named_parameters()}
+            grads_before = {n: None if t.grad is None else t.grad.clone() for n, t in m.named_parameters()}
+            step = GradCacheStep(m, chunk_size=2, precision=pol)
+            try:
+                step(dict(q), dict(p)); det[f"{pol}_raises"] = False
+            except GritHipError as ex:
+                det[f"{pol}_raises"] = "fp16 range" in str(ex) and pol in str(ex) and "cuda" in str(ex)
+            ok &= det[f"{pol}_raises"] is True
+            untouched = all(torch.equal(t, params[n]) for n, t in m.named_parameters())
+            nograd = all((t.grad is None) if grads_before[n] is None else (t.grad is not None and torch.equal(t.grad, grads_before[n]))
+                         for n, t in m.named_parameters())
+            det[f"{pol}_params_untouched"] = untouched; det[f"{pol}_no_grad_written"] = nograd
+            ok &= untouched and nograd
+            m.train_engine.set_nograd_precision("bf16")
+            lv = float(step(dict(q), dict(p)).item())
+            det[f"{pol}_then_bf16_loss_equal"] = lv == ref_loss; ok &= lv == ref_loss
+            del m, step
+            torch.cuda.empty_cache()
+        # stale flag: set by an overflowing fp16 GEMM before a tame fp16 step
+        m = model(dt)
+        big = fh(np.full((64, 128), 200.0, dtype=np.float32)); wt = fh(np.full((128, 128), 4.0, dtype=np.float32))
+        ops.gemm_nt(big, wt)
+        det["stale_flag_set"] = _f16_flag(clear=False); ok &= det["stale_flag_set"]
+        try:
+            lt = float(GradCacheStep(m, chunk_size=2, precision="f16_operands")(dict(q), dict(p)).item())
+            det["stale_flag_not_blamed"] = bool(np.isfinite(lt))
+        except GritHipError:
+            det["stale_flag_not_blamed"] = False
+        ok &= det["stale_flag_not_blamed"]
+        del m
+        torch.cuda.empty_cache()
+    return _res(f"GradCache fp16 pass-1 overflow raises before any gradient [{cfg_name}]", bool(ok), ref_loss=ref_loss, **det)
+
+
 ALL_CHECKS = [
     ("embed", check_embed, {}),
     ("rmsnorm_4096", check_rmsnorm, dict(T=37, H=4096)),
@@ -4232,6 +4680,16 @@ ALL_CHECKS = [
     ("gemv_expert_8x7b_w13_strides", check_gemv_expert, dict(big=True)),
     ("native_generate_moe", check_native_generate, dict(cfg_name="moe-tiny", P=9, new=6, rows=2, tol=0.08)),
     ("native_generate_moe_f16", check_native_generate_f16, dict(cfg_name="moe-tiny", P=9, new=6, rows=2, policy="f16_operands", cos_bound=2e-5)),
+    ("moe_router_edges", check_moe_router_edges, {}),
+    ("moe_router_edges_e4", check_moe_router_edges, dict(E=4)),
+    ("moe_router_edges_e16", check_moe_router_edges, dict(E=16, H=512)),
+    ("moe_index_multichunk", check_moe_index_multichunk, {}),
+    ("gemv_expert_index_clamped", check_gemv_expert_index_clamped, {}),
+    ("gemv_expert_index_clamped_8x7b_w13_strides", check_gemv_expert_index_clamped, dict(big=True)),
+    ("mixtral_f16_overflow_encode", check_mixtral_f16_overflow_encode, {}),
+    ("mixtral_f16_overflow_encode_gqa", check_mixtral_f16_overflow_encode, dict(cfg_name="moe-gqa")),
+    ("gradcache_f16_overflow", check_gradcache_f16_overflow, {}),
+    ("gradcache_f16_overflow_moe", check_gradcache_f16_overflow, dict(cfg_name="moe-tiny")),
     ("generate_native_api", check_generate_native_api, {}),
     ("native_generate_prompt_chunk", check_native_generate_prompt_chunk, {}),
     ("native_generate_prompt_chunk_f16", check_native_generate_prompt_chunk, dict(policy="f16_stream")),

@@ -177,14 +177,15 @@ def build_mistral_dir(path: str, cfg_name="tiny", seed: int = 0, dtype="float32"
     return path
 
 
-def build_mixtral_dir(path: str, cfg_name: str = "moe-tiny", seed: int = 0, dtype="float32") -> str:
-    """MixtralForCausalLM with the synthetic weights of make_weights (reference names block_sparse_moe.experts.N.w1/w2/w3 mapped to the
-    installed transformers' fused gate_up_proj / down_proj parameters) + tokenizer, saved to ``path``."""
+def build_mixtral_dir(path: str, cfg_name: str = "moe-tiny", seed: int = 0, dtype="float32", weights: dict | None = None) -> str:
+    """MixtralForCausalLM with the synthetic weights of make_weights (or the given ``weights``; reference names
+    block_sparse_moe.experts.N.w1/w2/w3 mapped to the installed transformers' fused gate_up_proj / down_proj parameters) + tokenizer,
+    saved to ``path``."""
     import torch
     from transformers import MixtralForCausalLM
     cfg = CONFIGS[cfg_name]
     model = MixtralForCausalLM(hf_config(cfg))
-    w = make_weights(cfg, seed)
+    w = make_weights(cfg, seed) if weights is None else weights
     E = cfg["num_local_experts"]
     sd = {}
     for k, v in w.items():

@@ -82,6 +82,26 @@ def test_bad_arguments_of_the_widened_entry_points():
     assert lib.grit_knn_workspace_bytes(4, 10000, 10) > 4 * 10000 * 4
 
 
+def test_gemv_expert_validates_the_expert_count():
+    """ABI 6: grit_gemv_{bf16,f16}_expert take the stack's expert count E (the kernel clamps the device-read index to [0, E)).  E < 1 and
+    an E whose last matrix offset (E - 1) * w_expert_stride overflows are refused before any launch; the stride check still holds."""
+    lib = _lib.load()
+    buf = (ctypes.c_char * 8192)()
+    p16 = (ctypes.addressof(buf) + 15) & ~15
+    B = _lib.GRIT_E_BADARG
+    N, K = 64, 64
+    for fn in (lib.grit_gemv_bf16_expert, lib.grit_gemv_f16_expert):
+        call = lambda E, stride=N * K, epi=0: fn(p16, p16, p16, p16, stride, E, 1, N, K, K, K, N, epi, None)
+        for bad_e in (0, -1, -2**31):
+            assert call(bad_e) == B, bad_e
+            assert b"expert count" in lib.grit_last_error_string()
+        assert call(2**31 - 1, stride=2**40) == B                                        # (E - 1) * stride beyond int64
+        assert b"expert count" in lib.grit_last_error_string()
+        assert call(4, stride=N * K - 8) == B                                             # stride < N * ldw (unchanged check)
+        assert b"bad sizes" in lib.grit_last_error_string()
+        assert call(4, epi=1) == B                                                        # RESIDUAL is not offered
+
+
 def test_ops_refuse_cpu_tensors_loudly():
     import torch
     from gritlm_amd import ops

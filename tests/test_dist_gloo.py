@@ -149,6 +149,57 @@ def test_two_rank_gather_schedule_does_not_depend_on_a_ranks_padding(tmp_path):
         assert abs(ret[r]["loss"] - float(g["loss_gradcache"])) < 2e-4
 
 
+def _gc_overflow_worker(rank, world, port, model_dir, ret):
+    """Rank 1 alone reads its fp16 overflow flag as set after pass 1 (the step's policy and its flag-reading seam patched: gloo has no
+    fp16 kernels).  The ranks agree over the process group, so BOTH raise, before the loss or any gradient is computed."""
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        torch.set_num_threads(2)
+        from gritlm_amd._lib import GritHipError
+        from gritlm_amd.training import GradCacheStep, GritLMTrainModel
+        g = np.load(os.path.join(GOLDEN, "gradcache_tiny.npz"))
+        m = GritLMTrainModel(model_name_or_path=model_dir, mode="embedding", pooling_method="mean", normalized=True, attn="bbcc",
+                             temperature=0.02, negatives_cross_device=True, device="cpu")
+        m.model.train()
+        B, G = g["q_ids"].shape[0], int(g["group"])
+        bq = B // world
+        sl_q, sl_p = slice(rank * bq, (rank + 1) * bq), slice(rank * bq * G, (rank + 1) * bq * G)
+        q = {"input_ids": torch.from_numpy(g["q_ids"][sl_q]), "attention_mask": torch.from_numpy(g["q_mask"][sl_q])}
+        p = {"input_ids": torch.from_numpy(g["p_ids"][sl_p]), "attention_mask": torch.from_numpy(g["p_mask"][sl_p])}
+        step = GradCacheStep(m, chunk_size=2)
+        step.precision = "f16_operands"
+        reads = []
+        def read_flag(clear=True):
+            reads.append(clear)
+            return rank == 1
+        step._read_f16_flag = read_flag
+        try:
+            step(q, p)
+            raised = ""
+        except GritHipError as ex:
+            raised = str(ex)
+        ret[rank] = dict(raised=raised, reads=len(reads), grads=sum(t.grad is not None for t in m.model.parameters()))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_rank_gradcache_fp16_overflow_raises_on_every_rank(tmp_path):
+    """An fp16 pass-1 overflow on ONE rank makes every rank raise GritHipError (one MAX all-reduce of the flag after the gathers), none
+    hangs in a collective the other skipped, and no parameter gradient is written on either rank."""
+    import synth
+    d = synth.build_mistral_dir(str(tmp_path / "m32"), "tiny", 0, "float32")
+    world = 2
+    mgr = mp.Manager(); ret = mgr.dict()
+    mp.spawn(_gc_overflow_worker, args=(world, _free_port(), d, ret), nprocs=world, join=True)
+    for r in range(world):
+        msg = ret[r]["raised"]
+        assert "fp16 range" in msg and "f16_operands" in msg and "bf16" in msg, (r, msg)
+        assert ret[r]["reads"] == 2                 # cleared before pass 1, read after it
+        assert ret[r]["grads"] == 0, r
+    assert "rank 1" in ret[0]["raised"] and "rank 1" in ret[1]["raised"]      # both name the rank whose device overflowed
+
+
 def _enc_worker(rank, world, port, model_dir, sents, ret):
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)

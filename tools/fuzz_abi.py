@@ -29,5 +29,19 @@ for name, (res, args) in _lib._SIGNATURES.items():
         r = fn(*vals)
         total += 1
         codes[int(r) if r is not None else None] = codes.get(int(r) if r is not None else None, 0) + 1
+# the expert-indexed GEMVs' stack description (ABI 6: E beside w_expert_stride) with every other argument valid: extreme E x stride pairs
+# must be refused by the shim (E < 1, (E - 1) * stride beyond int64) before any launch
+p16 = (addr + 15) & ~15
+for name in ("grit_gemv_bf16_expert", "grit_gemv_f16_expert"):
+    fn = getattr(lib, name)
+    for _ in range(N):
+        E = random.choice(ints + [3, 5, 16, 17])
+        stride = random.choice(longs + [64 * 64, 2**62, 2**63 - 8])
+        if not (E < 1 or (E > 1 and stride > (2**63 - 1) // (E - 1))):
+            continue                  # a valid stack description would pass on to a launch: only the refused ones are called
+        r = fn(p16, p16, p16, p16, stride, E, 1, 64, 64, 64, 64, 64, 0, None)
+        total += 1
+        codes[int(r)] = codes.get(int(r), 0) + 1
+        assert r == _lib.GRIT_E_BADARG, (name, E, stride, r)
 neg = {k: v for k, v in codes.items() if k is not None and k < 0}
 print("calls", total, "negative return codes", dict(sorted(neg.items())), "zero", codes.get(0, 0), "positive", sum(v for k, v in codes.items() if k and k > 0))
