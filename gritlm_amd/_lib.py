@@ -76,6 +76,9 @@ _SIGNATURES = {
     "grit_moe_decode_combine_f32": (_i, [_p, _p, _p, _p, _i, _i, _p]),
     "grit_rope_kv_append_rows": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _i, _p]),
     "grit_attn_decode_rows": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _f, _i, _p]),
+    "grit_kv_append_chunk": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _p]),
+    "grit_attn_prefill_cached_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _f, _p]),
+    "grit_attn_prefill_cached_f16_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _f, _p]),
     "grit_knn_workspace_bytes": (_l, [_i, _l, _i]),
     "grit_knn_topk": (_i, [_p, _p, _i, _l, _i, _l, _l, _i, _p, _p, _p, _p]),
     "grit_ce_fwd": (_i, [_p, _l, _p, _p, _p, _l, _i, _p]),

@@ -23,6 +23,31 @@ from .encoder import F16_POLICIES, MistralEncoderEngine, rope_tables
 BF16, F16, F32, I32, I64 = torch.bfloat16, torch.float16, torch.float32, torch.int32, torch.int64
 
 
+PREFILL_MODES = ("rows", "gemm")
+
+
+def prefill_layout(attention_mask: torch.Tensor, lens: torch.Tensor, Lmax: int | None = None):
+    """The geometry of a right-padded prompt chunk on top of cached prefixes (pure tensor arithmetic, any device): ``attention_mask`` [B,P]
+    over the chunk's tokens, ``lens`` [B] the cached prefix length of every row.  Returns (plen int32 [B]: valid tokens per row;
+    positions int32 [B*P]: lens[b] + i of every chunk row, padding rows included, clamped below ``Lmax``; last int64 [B]: the flattened row
+    b*P + plen[b] - 1 of every row's last valid token).  A mask that is not right-padded (left padding, holes) or a row without a token
+    raises NotImplementedError."""
+    m = attention_mask != 0
+    B, P = m.shape
+    plen = m.sum(dim=1)
+    ar = torch.arange(P, device=m.device).view(1, P)
+    if not bool(((ar < plen.view(B, 1)) == m).all()):
+        raise NotImplementedError("native decode: prompt rows on top of past_key_values must be right-padded (a mask of 1 ... 1 0 ... 0 per row)")
+    if not bool((plen > 0).all()):
+        raise NotImplementedError("native decode: every prompt row on top of past_key_values needs at least one token")
+    lens = lens.to(device=m.device, dtype=torch.int64).view(B, 1)
+    positions = lens + ar
+    if Lmax is not None:
+        positions = positions.clamp(max=Lmax - 1)
+    last = torch.arange(B, device=m.device, dtype=torch.int64) * P + plen.to(torch.int64) - 1
+    return plen.to(I32), positions.reshape(B * P).to(I32), last
+
+
 def _layers_of(cache):
     """per-layer (k, v) [B, nkv, S, d] from the installed transformers' cache object or a legacy tuple of tuples."""
     if hasattr(cache, "layers"):
@@ -59,6 +84,13 @@ class MistralDecoder:
         # rows x splits) the loop is used.
         self.prompt_chunk = os.environ.get("GRIT_DECODE_PROMPT_CHUNK", "1") != "0" and not self.moe
         self.prompt_chunk_max_rows = 512
+        # prompt tokens on top of past_key_values, the path: "rows" (the default: the decode step's kernels above, or the token loop) or
+        # "gemm" (the encoder engine's MFMA GEMMs over the whole chunk, grit_attn_prefill_cached_*: MistralEncoderEngine.forward_on_cache;
+        # right-padded rows supported).  GRIT_DECODE_PREFILL sets it.
+        self.prefill = os.environ.get("GRIT_DECODE_PREFILL", "rows")
+        if self.prefill not in PREFILL_MODES:
+            raise ValueError(f"GRIT_DECODE_PREFILL={self.prefill!r}: one of {PREFILL_MODES}")
+        self.last_prefill = None                  # the prompt path of the last generate() call: "encoder" | "rows" | "tokens" | "gemm"
         self._lm_head16 = None
         self.last_precision = None                # what the last generate() call ran in ("bf16" | "f16"; "bf16 (f16 overflow)" after a fallback)
 
@@ -238,6 +270,30 @@ class MistralDecoder:
         ops.rmsnorm_gemv(last, e.norm, eps, self._lm_head_f16() if f16 else self.lm_head, out=st["logits"], deferred=True)
         st["lens"] += P
 
+    def _prompt_gemm(self, st, ids: torch.Tensor, mask: torch.Tensor):
+        """The prompt chunk through the encoder engine's GEMMs on top of the cache (MistralEncoderEngine.forward_on_cache; the engine's
+        policy switched for the pass as in the past=None prefill), the first logits from each row's last valid token through the same
+        launch the past=None prefill uses; advances lens by each row's valid length."""
+        c, e, dev = self.cfg, self.eng, self.device
+        f16 = st["f16"]
+        Lmax = st["cache"][0][0].shape[2]
+        plen, pos, last = prefill_layout(mask, st["lens"], Lmax)
+        plen, pos, last = plen.to(dev), pos.to(dev), last.to(dev)
+        pol = e.precision
+        if f16 and pol not in F16_POLICIES:
+            e.precision = "f16_operands"
+        elif not f16 and pol in F16_POLICIES:
+            e.precision = "bf16"
+        try:
+            hl = e.forward_on_cache(ids, st["cache"], st["lens"], plen, pos, last, final_norm=not f16)
+        finally:
+            e.precision = pol
+        if f16:
+            ops.rmsnorm_gemv(hl.to(F16), e.norm, c.rms_norm_eps, self._lm_head_f16(), out=st["logits"], deferred=True)
+        else:
+            ops.gemv(hl, self.lm_head, out=st["logits"])
+        st["lens"] += plen
+
     def _sample(self, st):
         ops.argmax_advance(st["logits"], st["next"], st["lens"], st["history"], st["step"])
 
@@ -267,8 +323,8 @@ class MistralDecoder:
                  past_lens: torch.Tensor | None = None, eos_token_id: int | None = None, return_logits: bool = False,
                  on_overflow: str | None = None, _force_bf16: bool = False):
         """Greedy continuation.  ``input_ids`` [B,P]: the NEW prompt tokens (right-padded rows need ``attention_mask``; with
-        ``past_key_values`` all rows must be full length).  ``past_key_values``: per-layer K/V [B,nkv,S,d] of an already encoded
-        prefix, e.g. the bidirectional document pass of ``encode(get_cache=True)``; ``past_lens`` [B] = valid prefix tokens per row
+        ``past_key_values`` all rows must be full length under ``prefill="rows"``, right-padded under ``"gemm"``).
+        ``past_key_values``: per-layer K/V [B,nkv,S,d] of an already encoded prefix, e.g. the bidirectional document pass of ``encode(get_cache=True)``; ``past_lens`` [B] = valid prefix tokens per row
         (default S).  Returns the generated ids [B, max_new_tokens] (int64; positions after ``eos_token_id`` keep that id) and, with
         ``return_logits``, the logits of every generated position [B, max_new_tokens, V] (bf16; fp32 on fp16 operands).
 
@@ -276,6 +332,8 @@ class MistralDecoder:
         ``GritHipError``, ``"bf16"`` repeats the whole call in the bf16 arithmetic; default ``self.on_overflow`` ("raise";
         ``GritLM(precision="auto").native_decoder()`` sets "bf16": the ladder's last rung)."""
         dev, c = self.device, self.cfg
+        if self.prefill not in PREFILL_MODES:
+            raise ValueError(f"MistralDecoder.prefill={self.prefill!r}: one of {PREFILL_MODES}")
         f16 = self._f16() and not _force_bf16
         on_overflow = self.on_overflow if on_overflow is None else on_overflow
         if on_overflow not in ("raise", "bf16"):
@@ -320,11 +378,22 @@ class MistralDecoder:
                 st["cache"][li][0][:, :, :P].copy_(k); st["cache"][li][1][:, :, :P].copy_(v)
             plen = mask.sum(dim=1).to(I32)
             st["lens"].copy_(plen)
+            self.last_prefill = "encoder"
             last = hidden[torch.arange(B, device=dev), (plen - 1).long()].contiguous()              # [B,H] of the last prompt token
             if f16:
                 ops.rmsnorm_gemv(last.to(F16), self.eng.norm, c.rms_norm_eps, self._lm_head_f16(), out=st["logits"], deferred=True)
             else:
                 ops.gemv(last, self.lm_head, out=st["logits"])                                       # (final-norm output, bf16)
+        elif self.prefill == "gemm" and P > 0:
+            mask = torch.ones((B, P), dtype=I64, device=dev) if attention_mask is None else attention_mask.to(device=dev, dtype=I64)
+            prefill_layout(mask, torch.zeros((B,), dtype=I32, device=dev))        # (refuses a mask that is not right-padded before anything runs)
+            for li, (k, v) in enumerate(past):
+                st["cache"][li][0][:, :, :S0].copy_(k.to(dev)); st["cache"][li][1][:, :, :S0].copy_(v.to(dev))
+            if f16 and any(k.dtype != F16 or v.dtype != F16 for k, v in past):
+                self._flag_nonfinite_cache(st, S0)
+            st["lens"].copy_(torch.full((B,), S0, dtype=I32, device=dev) if past_lens is None else past_lens.to(device=dev, dtype=I32))
+            self._prompt_gemm(st, ids, mask)
+            self.last_prefill = "gemm"
         else:
             if attention_mask is not None and not bool((attention_mask != 0).all()):
                 raise NotImplementedError("native decode: padded prompt rows on top of past_key_values")
@@ -337,11 +406,13 @@ class MistralDecoder:
             # exact-norm forms and very long prompts, one token per step (teacher forced); its K/V land behind the cached prefix
             if P > 0 and self.prompt_chunk and (f16 or self.fuse_norm == "deferred") and B * P <= self.prompt_chunk_max_rows:
                 self._prompt_rows(st, ids)
+                self.last_prefill = "rows"
             else:
                 for t in range(P):
                     st["next"].copy_(ids[:, t])
                     self._step(st)
                     st["lens"] += 1
+                self.last_prefill = "tokens"
         # first generated token from the prefill logits, then decode steps (graph replay)
         if return_logits:
             logits_all[:, 0].copy_(st["logits"])

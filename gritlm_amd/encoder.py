@@ -483,6 +483,50 @@ class MistralEncoderEngine:
 
     __call__ = forward
 
+    # ------------------------------------------------------------------ a prompt chunk on top of a K/V cache
+    @torch.no_grad()
+    def forward_on_cache(self, input_ids: torch.Tensor, cache: list, lens: torch.Tensor, plen: torch.Tensor, positions: torch.Tensor,
+                         last: torch.Tensor, final_norm: bool = True) -> torch.Tensor:
+        """The layer loop of ``forward`` for a chunk of P prompt tokens per sequence BEHIND a cached prefix (causal, the reference's sdpa
+        attention with a cache: modeling_mistral_gritlm.py:619-705, :1005-1036).  ``input_ids`` [B,P] right-padded; ``cache``: per layer
+        (k, v) [B,nkv,Lmax,d] in the policy's operand format (bf16; fp16 under the fp16 policies); ``lens`` int32 [B] cached prefix per row,
+        ``plen`` int32 [B] valid chunk rows, ``positions`` int32 [B*P] (lens[b] + i, below Lmax), ``last`` int64 [B] the flattened row of each
+        sequence's last valid token (``decoder.prefill_layout``).  Per layer: RMSNorm -> q|k|v GEMM with RoPE at ``positions`` -> the
+        chunk's k / v into the cache at lens[b] + i (grit_kv_append_chunk) -> attention over keys 0 .. lens[b] + i
+        (grit_attn_prefill_cached_*) -> o_proj + residual -> RMSNorm -> MLP, each under the engine's policy.  ``lens`` is NOT advanced.
+        Returns [B,H]: the final-norm output (bf16) of every sequence's last valid token, or with ``final_norm=False`` its residual stream."""
+        c = self.cfg
+        if c.num_local_experts:
+            raise NotImplementedError("forward_on_cache: sparse-MoE (Mixtral) prefill on a cache is not built")
+        B, P = input_ids.shape
+        T = B * P
+        Lmax = cache[0][0].shape[2]
+        if self.causal and 0 < self.window_keys < Lmax:
+            raise NotImplementedError("forward_on_cache: full causal attention over the cache only (window_keys = 0)")
+        if self.precision in F16_POLICIES:
+            self.set_precision(self.precision)
+        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        ws = self._workspace(T)
+        h, x, qkv, ctx = ws["h"], ws["x"], ws["qkv"], ws["ctx"]
+        if cache[0][0].dtype != qkv.dtype:
+            raise TypeError(f"forward_on_cache: the cache holds {cache[0][0].dtype}, precision '{self.precision}' writes {qkv.dtype} K/V")
+        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
+        cos, sin = self._rope_tables(Lmax)
+        ops.embed_gather(self._embed_table(), ids, out=h)
+        for L, (ck, cv) in zip(self.layers, cache):
+            wqkv, wo = self._weights(L)[:2]
+            ops.rmsnorm(h, L.ln1, eps, out=x)
+            ops.gemm_nt_rope(x, wqkv, cos, sin, (nq + nkv) * d, positions=positions, out=qkv)
+            ops.kv_append_chunk(qkv, ck, cv, lens, plen, nq, nkv, d)
+            ops.attn_prefill_cached(qkv, ck, cv, lens, plen, nq, nkv, d, out=ctx)
+            ops.gemm_nt(ctx, wo, out=h, epilogue=self._epi_res(), residual=h)
+            ops.rmsnorm(h, L.ln2, eps, out=x)
+            self._mlp(L, x, h, ws)
+        hl = h.index_select(0, last)
+        if not final_norm:
+            return hl
+        return ops.rmsnorm(hl, self.norm, eps, out=torch.empty((B, c.hidden_size), dtype=BF16, device=self.device))
+
     # ------------------------------------------------------------------ packed (un-padded) forward
     @staticmethod
     def is_right_padded(attention_mask: torch.Tensor) -> bool:

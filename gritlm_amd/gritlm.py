@@ -300,7 +300,11 @@ class GritLM(torch.nn.Module):
         reference's [B, cache + P] mask, ones over the cache), returned like Hugging Face's ``generate``: the input ids followed by the new
         tokens, positions after a sequence's EOS filled with ``pad_token_id``.  ``min_new_tokens`` is honoured when it equals
         ``max_new_tokens`` (the reference's latency runs: EOS never stops a row) or is 0; sampling, beams and other generation options are
-        not native -- ``GritLM.generate`` (the Hugging Face method) stays available for them."""
+        not native -- ``GritLM.generate`` (the Hugging Face method) stays available for them.
+
+        Long inputs on top of a cache (the reference's query caching, rag/eval.py:200-238: the passage plus the prompt behind the query's
+        cached K/V): ``m.native_decoder().prefill = "gemm"`` (or GRIT_DECODE_PREFILL=gemm) runs them through the encoder's MFMA GEMMs
+        instead of the decode kernels, and accepts batched, right-padded inputs (the tail of ``attention_mask``)."""
         if do_sample or unsupported:
             raise NotImplementedError(f"generate_native: greedy decoding only (got do_sample={do_sample}, {sorted(unsupported)}); use GritLM.generate")
         if min_new_tokens not in (0, max_new_tokens):

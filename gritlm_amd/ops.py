@@ -775,6 +775,41 @@ def attn_decode_rows(q: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tens
     return out
 
 
+def kv_append_chunk(qkv: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, lens: torch.Tensor, plen: torch.Tensor, nq: int, nkv: int,
+                    d: int):
+    """The k / v heads of a prompt chunk's fused q|k|v rows [B*P, stride] (post-RoPE) -> cache rows lens[b] + i, i < plen[b]; the rows
+    and the caches [B,nkv,Lmax,d] share one 16-bit format (bf16, or fp16 under the fp16 policies)."""
+    B, _, Lmax, _ = cache_k.shape
+    T = qkv.shape[0]
+    dt = cache_k.dtype
+    assert T % B == 0 and lens.numel() == B and plen.numel() == B
+    check(_lib.load().grit_kv_append_chunk(_chk2d(qkv, dt, "qkv"), _chk(cache_k, dt, "cache_k"), _chk(cache_v, dt, "cache_v"), _chk(lens, I32, "lens"),
+                                           _chk(plen, I32, "plen"), B, T // B, nq, nkv, d, Lmax, qkv.stride(0), _stream()), "grit_kv_append_chunk")
+
+
+def attn_prefill_cached(q: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, lens: torch.Tensor, plen: torch.Tensor, nq: int, nkv: int,
+                        d: int, out: torch.Tensor | None = None, scale: float | None = None) -> torch.Tensor:
+    """Attention of a prompt chunk over the cache: ``q`` [B*P, stride] (the fused q|k|v rows: the q heads are read), query (b, i) attends to
+    keys 0 .. lens[b] + i of sequence b; rows i >= plen[b] come back as zeros.  bf16 or fp16 (the caches' format)."""
+    B, _, Lmax, _ = cache_k.shape
+    T = q.shape[0]
+    dt = cache_k.dtype
+    assert T % B == 0 and lens.numel() == B and plen.numel() == B
+    if out is None:
+        out = torch.empty((T, nq * d), dtype=dt, device=q.device)
+    fn = _lib.load().grit_attn_prefill_cached_f16_fwd if dt == F16 else _lib.load().grit_attn_prefill_cached_fwd
+    # (work: the keys each valid query sees, lens[b] + i + 1 -- device data, read after the timed region)
+    ev = _timer.span("attn_prefill_cached", (4.0 * nq * d * plen.double() * (lens.double() + (plen.double() + 1) / 2)).sum()) if _timer is not None else None
+    if ev:
+        ev[0].record()
+    check(fn(_chk2d(q, dt, "q"), _chk(cache_k, dt, "cache_k"), _chk(cache_v, dt, "cache_v"), _chk(lens, I32, "lens"), _chk(plen, I32, "plen"),
+             _chk2d(out, dt, "out"), B, T // B, nq, nkv, d, Lmax, q.stride(0), out.stride(0), float(d ** -0.5 if scale is None else scale), _stream()),
+          "grit_attn_prefill_cached_fwd")
+    if ev:
+        ev[1].record()
+    return out
+
+
 def argmax_advance(logits: torch.Tensor, next_ids: torch.Tensor, lens: torch.Tensor | None = None, history: torch.Tensor | None = None,
                    step: torch.Tensor | None = None):
     B, V = logits.shape

@@ -486,6 +486,23 @@ int grit_attn_decode_rows(const void* q, const void* cache_k, const void* cache_
                           float* workspace, int V, int nq, int nkv, int d, int Lmax, int64_t q_stride, int64_t out_stride, float scale,
                           int f16, void* stream);
 
+/* ---- prompt prefill on cached K/V (native decoder, prefill "gemm"): a chunk of P prompt tokens per sequence behind a cached prefix, run
+ * through the encoder's MFMA GEMMs -- the reference's sdpa attention with a cache and the causal mask offset by the past length
+ * (scripts/modeling_mistral_gritlm.py:619-705, :1005-1036).  Chunk row (b, i) is row b*P + i of the fused q|k|v buffer that
+ * grit_gemm_*_nt_rope wrote with positions lens[b] + i; lens int32 [B] = cached prefix length per sequence (may be 0), plen int32 [B] = valid
+ * chunk rows per sequence (right padding; 1 <= plen[b] <= P); caches [B, nkv, Lmax, 128] (the decoder's layout), bf16 or fp16.
+ * grit_kv_append_chunk copies the chunk's (already rotated) k / v heads to cache rows lens[b] + i, i < plen[b] (a 16-bit copy: either
+ * format; rows that would land at or past Lmax are not written).  grit_attn_prefill_cached_fwd (bf16) / _f16_fwd (fp16): query (b, i)
+ * attends to keys 0 .. lens[b] + i of sequence b (GQA by index; q = the fused buffer's q heads, row stride q_stride); out [B*P, out_stride]
+ * in the same format, rows i >= plen[b] written as zeros.  No LSE. */
+int grit_kv_append_chunk(const void* qkv, void* cache_k, void* cache_v, const int32_t* lens, const int32_t* plen, int B, int P, int nq, int nkv,
+                         int d, int Lmax, int64_t qkv_stride, void* stream);
+int grit_attn_prefill_cached_fwd(const void* q, const void* cache_k, const void* cache_v, const int32_t* lens, const int32_t* plen, void* out,
+                                 int B, int P, int nq, int nkv, int d, int Lmax, int64_t q_stride, int64_t out_stride, float scale, void* stream);
+int grit_attn_prefill_cached_f16_fwd(const void* q, const void* cache_k, const void* cache_v, const int32_t* lens, const int32_t* plen, void* out,
+                                     int B, int P, int nq, int nkv, int d, int Lmax, int64_t q_stride, int64_t out_stride, float scale,
+                                     void* stream);
+
 /* ---- RAG index search: rag/index.py:97-104 (scores = queries @ embeddings; torch.topk) ------------------------ */
 
 /* Brute-force kNN by inner product.  queries [Q,H] fp32 (contiguous); embeddings: element (n,h) at n*emb_stride_n + h*emb_stride_h, so
