@@ -9,41 +9,13 @@
 // its Q rows are fetched into the same registers, under the last tile of the current one), so the per-block prologue (Q + first-tile latency) is paid once
 // per workgroup and the output stores of a block drain under the next block's first tile.  Workgroups that share K/V (the GQA
 // group's heads x query-block groups of one (batch, kv head)) are dealt to the SAME XCD back to back (block v runs on XCD v % 8).
-// KV tiles of 64 keys go HBM -> LDS by direct LDS-DMA (buffer_load ... lds, 16 B per lane, 1 KiB = 4 key rows per wave instruction;
-// the descriptor's range check zero-fills rows past the sequence) into a two-stage ring: the eight pieces of tile t+1 are issued
-// BETWEEN the QK products of tile t and land under its softmax and PV products -- no staging registers, no ds_write pass, one barrier
-// per tile.  Every LDS fragment read of the tile loop is inline asm with counted lgkmcnt (round 3): K fragments two k-slices ahead of
-// their products, V fragments in four groups of 8 with the first two requested in front of the softmax; nothing in the loop makes hipcc
-// wait for more than it needs (its own lgkmcnt(0) / vmcnt(0) in front of builtin LDS reads, scalar loads and ds_bpermute cost 12 %).  Both images are row-major [key][256 B] with the 16-byte
-// units XOR-swizzled through the per-lane SOURCE address (the LDS image of a DMA is lane-linear): K unit ^= key & 15
-// (conflict-free ds_read_b128 of a 32-key fragment), V unit ^= 4 (key & 3) (conflict-free ds_read_b64_tr_b16: the 16 lanes of a
-// transposing read touch 4 keys x 32 B, the XOR puts them -- and the second 16-lane group -- on 16 distinct units of one 256-B bank row).
-//   S^T = K Q^T     v_mfma_f32_32x32x16_bf16(A = K rows, B = Q)  -> lane (q = lane&31) holds 32 keys' scores
-//   O^T = V^T P^T   v_mfma_f32_32x32x16_bf16(A = V^T rows, B = P) -> lane (q = lane&31) holds 64 of its d's
-// Both products are "swapped" so that every softmax statistic (max, sum, rescale) is lane-local: the only
-// cross-lane traffic per tile is one v_permlane32_swap for the row max.  The P operand needs no
-// permlane/LDS round trip: the MFMA contraction index is permuted identically on the V^T side
-// (key(kb,c,hi,j) = 32kb + 16c + 8(j>>2) + 4hi + (j&3)): two transposing 8-byte LDS reads whose per-lane
-// addresses select exactly those keys.
+// The tile loop itself -- LDS-DMA ring, swizzled K / V images, counted inline-asm LDS reads, the swapped products and the online
+// softmax -- and the output epilogue are attn_tile.h, shared with the cached-K/V prefill (prefill.hip); this file holds the tile
+// ranges, the key masks, the buffer-addressed K/V staging, the Q staging and the block seam.
 #include <stdlib.h>
 
-#include <atomic>
+#include "attn_tile.h"
 
-#include "common.h"
-
-// s_waitcnt vmcnt(0) through the builtin (gfx9 encoding: expcnt 7, lgkmcnt 15 = "don't wait"): unlike an asm statement the waitcnt
-// insertion pass SEES it, so it does not add its own vmcnt(0) in front of the first MFMA that reads the re-fetched Q registers -- that
-// wait would sit behind the freshly issued DMA of the next tile and serialise it
-#define ATT_WAIT_VM0()                      \
-  do {                                      \
-    asm volatile("" ::: "memory");          \
-    __builtin_amdgcn_s_waitcnt(0x0F70);     \
-    asm volatile("" ::: "memory");          \
-  } while (0)
-
-#ifndef ATT_DEFER_MAX
-#define ATT_DEFER_MAX 1
-#endif
 // ATT_TIMING (diagnostic build, tools/attn_phase_probe.sh): thread 0 of every workgroup writes s_memtime stamps (cycles since kernel entry) as
 // raw u32 into the workgroup's LSE rows instead of the LSE -- where a workgroup's time goes between prologue, tiles, seams and stores
 // (profiles/r05_attn_phase_probe.json).  Three scheduling experiments built on that picture were measured and did NOT ship
@@ -55,29 +27,13 @@
 #else
 #define ATT_STAMP() do { } while (0)
 #endif
-// (ATT_DEFER_MAX and ATT_ABLATE_STORES are the A/B knobs of tools/ubench/attn_ab.cpp.  The levers of round 3 -- asm reads, spread /
+// (ATT_DEFER_MAX (attn_tile.h) and ATT_ABLATE_STORES are the A/B knobs of tools/ubench/attn_ab.cpp.  The levers of round 3 -- asm reads, spread /
 //  buffer-addressed / unconditional DMA pieces, early V reads, s_setprio over QK, xor K addresses, hoisted mask word, permlane row
 //  maximum -- were each A/B'd as a compile-time variant against the kernel of the previous commit, bit-identical every time
 //  (profiles/r03_attn_fwd_ab_asm_reads.log, 773 -> 870 TF at B 256 x S 512); the variants are resolved in this file, the round-2
 //  kernel is rebuilt from git history by tools/ubench/build_attn_ab.sh.)
 
 namespace grit {
-
-constexpr int ATT_D = 128;
-constexpr int ATT_QB = 128;   // query rows per workgroup
-constexpr int ATT_KB = 64;    // keys per tile
-constexpr int V_PITCH = 256;  // bytes per key row of the row-major V image
-constexpr int K_LDS_BYTES = ATT_KB * ATT_D * 2;  // 16384
-constexpr int V_LDS_BYTES = ATT_KB * V_PITCH;    // 16384
-constexpr int ATT_STAGE_BYTES = K_LDS_BYTES + V_LDS_BYTES;   // 32 KiB per stage, two stages
-constexpr int ATT_XPOSE_BYTES = 4096;                         // per wave: 32 rows x 128 B, the Q-in / O-out transposition buffer
-constexpr int ATT_LDS_BYTES = 2 * ATT_STAGE_BYTES + 4 * ATT_XPOSE_BYTES;   // 80 KiB: two workgroups fill the CU's 160 KiB exactly
-typedef const __attribute__((address_space(1))) void* att_gptr_t;
-typedef __attribute__((address_space(3))) void* att_lptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-
-__device__ __forceinline__ uint32_t lo16(uint32_t w) { return w & 0xffffu; }
-__device__ __forceinline__ uint32_t hi16(uint32_t w) { return w >> 16; }
 
 // VARLEN: sequences are packed back to back (no padding rows at all); cu_seqlens[b] is the first row of sequence b and
 // every key of a sequence is valid, so the key bitmask is synthesised from the length.
@@ -86,15 +42,7 @@ __device__ __forceinline__ uint32_t hi16(uint32_t w) { return w >> 16; }
 // CAUSAL with window > 0 (Mistral's sliding window, modeling_mistral_gritlm.py:381-385 / the sliding-window causal mask of
 // _prepare_4d_causal_attention_mask, :1005-1036): a query sees the `window` keys q - window + 1 .. q; tiles that lie wholly in front
 // of a query block's first visible key are skipped as well.
-// F16 (round 5, the encoder's "f16_operands" precision policy): q | k | v and the output hold IEEE fp16, P is rounded to fp16 --
-// v_mfma_f32_32x32x16_f16 runs at the bf16 rate, the LDS-DMA staging and the transposing reads are 16-bit-format-agnostic, so the
-// instruction stream is the bf16 one with the two MFMA opcodes and the two pack instructions exchanged.  The deferred rescale keeps
-// P <= 2^8, far inside the fp16 range; the output is a convex combination of V rows: nothing here can overflow.
-__device__ __forceinline__ f32x16_t mma32(bf16x8_t a, bf16x8_t b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16_t mma32(f16x8_t a, f16x8_t b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-template <bool F16> struct att_frag { typedef bf16x8_t type; };
-template <> struct att_frag<true> { typedef f16x8_t type; };
-
+// F16 (round 5, the encoder's "f16_operands" precision policy): q | k | v and the output hold IEEE fp16 (attn_tile.h).
 template <bool VARLEN, bool CAUSAL, bool F16 = false>
 __global__ void __launch_bounds__(256, 2)
 attn_bidir_fwd_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ key_bits, const int32_t* __restrict__ cu_seqlens,
@@ -214,10 +162,7 @@ attn_bidir_fwd_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ 
     const char* rp = xs + ql * 128;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[half * 4 + ks] = *reinterpret_cast<const frag_t*>(rp + (((2 * ks + hi) ^ q_swz) << 4));
-    // the reads must have left the buffer before it is refilled (DMA) or rewritten (O staging)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                           // lgkmcnt(0)
-    asm volatile("" ::: "memory");
+    ATT_WAIT_LGKM0();                           // the reads must have left the buffer before it is refilled (DMA) or rewritten (O staging)
   };
   // the workgroup's FIRST block takes its Q rows straight from global memory (row-per-lane loads, one round trip that overlaps the
   // first tile's DMA; two dependent passes through the 4 KiB buffer would put two memory latencies in front of the first product)
@@ -242,14 +187,8 @@ attn_bidir_fwd_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ 
       if (bits[w] != 0) { ntiles_all = w + 1; break; }
   }
 
-  // K fragment address: row = 32kb + (lane&31), d-slot = 2ks + hi, swizzle by row&15 == lane&15
-  const int kf_row = ql * 256, kf_x = lane & 15;
-  // V fragment (A operand of O^T += V^T P^T) straight from the ROW-MAJOR V image with ds_read_b64_tr_b16: in every 16-lane group lane j
-  // points at V[k0 + j/4][d0 + 4 (j%4)] and lane c receives V[k0 .. k0+3][d0 + c] (the hardware transposes the group's 4 x 16 block);
-  // d0 = 32db + 16 ((lane>>4)&1) makes c <-> the MFMA row lane&31, k0 = 32kb + 16c + 4hi (+8 for the second half of the k-slice)
-  // (key & 3) of every key a lane addresses is (lane>>2)&3, so the V swizzle turns the d-block offset db*64 into (db ^ r)*64, r = (lane>>2)&3:
-  // vt_lane carries r in byte bits 7:6 and the read address of d-block db is vt_lane ^ (db << 6)
-  const int vt_lane = (((lane & 15) >> 2) + 4 * hi) * V_PITCH + ((((lane >> 2) & 3) * 4) << 4) + (((lane >> 4) & 1) * 16 + 4 * (lane & 3)) * 2;
+  const int kf_row = ql * 256, kf_x = lane & 15;   // K / V fragment addresses (attn_tile.h)
+  const int vt_lane = ATT_VT_LANE(lane, hi);
 
   // KV tiles [t0, t1) of query block qb
   auto tile_range = [&](int qb, int& t0, int& t1) {
@@ -330,190 +269,17 @@ attn_bidir_fwd_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ 
         }
       }
 
-      // ---- S^T = K Q^T (scores for 64 keys x 32 q per wave)
-      // the two 32-key halves are two INDEPENDENT accumulation chains, issued alternately: a v_mfma_f32_32x32x16_bf16 occupies the pipe
-      // for 32 cycles but its result is ready after 64, so a product that accumulates onto the one issued just before it has to
-      // wait (hipcc keeps MFMA source order; A/B against "8 products on one half, then 8 on the other": +2.5-4.5 %, bit-identical)
       f32x16_t sacc[2];
-      // K fragments as inline-asm ds_read_b128 with counted lgkmcnt, requested two k-slices (2 reads each) ahead of the products that
-      // consume them (hipcc issues them in small batches and waits lgkmcnt(0) seven times per tile)
-      {
-        const f32x16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        // (2 ks + hi) ^ kf_x == (2 ks) ^ (hi ^ kf_x): one per-tile base with the lane's constant in address bits 7:4, one v_xor per k-slice
-        const uint32_t kbase = ((uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)k_lds) + (uint32_t)kf_row) | (uint32_t)((hi ^ kf_x) << 4);
-        frag_t kr[8][2];
-#define ATT_K_READ(KS)                                                                                                              \
-  do {                                                                                                                              \
-    const uint32_t ka = kbase ^ (uint32_t)((KS) << 5);                                                                              \
-    asm volatile("ds_read_b128 %0, %1" : "=v"(kr[KS][0]) : "v"(ka));                                                                \
-    asm volatile("ds_read_b128 %0, %1 offset:8192" : "=v"(kr[KS][1]) : "v"(ka));                                                    \
-  } while (0)
-#define ATT_K_MMA(KS, N)                                                                                                            \
-  do {                                                                                                                              \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(kr[KS][0]), "+v"(kr[KS][1]) : : "memory");                                      \
-    sacc[0] = mma32(kr[KS][0], qf[KS], (KS) == 0 ? zero16 : sacc[0]);                                                               \
-    sacc[1] = mma32(kr[KS][1], qf[KS], (KS) == 0 ? zero16 : sacc[1]);                                                               \
-    stage_piece(st_t, st_buf, (KS) >> 1, (KS) & 1);                                                                                 \
-    asm volatile("" ::: "memory");                                                                                                  \
-  } while (0)
-        // K fragments two k-slices ahead of their products (three ahead: no gain); one LDS-DMA piece of the next tile behind every
-        // product pair; s_setprio 1 over the section: 0 .. +2 % (over the PV section as well: -1.5 %)
-        __builtin_amdgcn_s_setprio(1);
-        ATT_K_READ(0); ATT_K_READ(1);
-        ATT_K_READ(2); ATT_K_MMA(0, 4);
-        ATT_K_READ(3); ATT_K_MMA(1, 4);
-        ATT_K_READ(4); ATT_K_MMA(2, 4);
-        ATT_K_READ(5); ATT_K_MMA(3, 4);
-        ATT_K_READ(6); ATT_K_MMA(4, 4);
-        ATT_K_READ(7); ATT_K_MMA(5, 4);
-        ATT_K_MMA(6, 2); ATT_K_MMA(7, 0);
-        __builtin_amdgcn_s_setprio(0);
-#undef ATT_K_READ
-#undef ATT_K_MMA
-      }
-
+      ATT_TILE_QK(k_lds)
       // the next block's Q rows replace this block's as soon as its last QK product has read them: the fetch lands under the
       // softmax and PV of the last tile, no second register set
       const bool q_next = more && t + 1 == ntiles;
-      if (q_next) {                 // this block's last QK products have read qf: refill it for the next block
+      if (q_next) {
         if (ntiles - t_first == 1) { q_stage_half(qb + 1, 0); ATT_WAIT_VM0(); }
         q_read_half(0);
         q_stage_half(qb + 1, 1);    // the other 64 columns land under the softmax and the PV products
       }
-
-      // The transposing V reads as inline asm with COUNTED lgkmcnt: hipcc's wait-count pass treats a ds_read_b64_tr_b16 builtin as aliasing the
-      // pending LDS-DMA and puts an s_waitcnt vmcnt(0) in front of the first one -- the NEXT tile's DMA then had to land before this
-      // tile's PV products could start.  Four groups (kb, c) of 8 reads feed 4 MFMAs each; group g + 1 is requested before group g is
-      // waited for (lgkmcnt(8): LDS returns in order), two register sets of 16.  The first two groups are requested HERE,
-      // in front of the softmax (the V tile has been in LDS since the barrier at the top of the tile; the K fragments' registers are free).
-      const uint32_t vbase = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)v_lds);
-      uint32_t va[4];
-#pragma unroll
-      for (int db = 0; db < 4; ++db) va[db] = vbase + (uint32_t)(vt_lane ^ (db << 6));
-      s16x4_t vr[2][4][2];
-#define ATT_TR_GROUP(G, BUF)                                                                                                          \
-  _Pragma("unroll") for (int db = 0; db < 4; ++db) {                                                                                  \
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(vr[BUF][db][0]) : "v"(va[db]), "i"(((G) >> 1) * 32 * V_PITCH + ((G) & 1) * 16 * V_PITCH));                \
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(vr[BUF][db][1]) : "v"(va[db]), "i"(((G) >> 1) * 32 * V_PITCH + ((G) & 1) * 16 * V_PITCH + 8 * V_PITCH)); \
-  }
-      {
-        int fast_i = __builtin_amdgcn_readfirstlane(fast ? 1 : 0);   // wave-uniform; made opaque HERE so that the compare -- and with it hipcc's wait for the
-        asm volatile("" : "+s"(fast_i));            // mask word's scalar load -- sits in front of the V reads, not behind them
-        fast = fast_i != 0;
-      }
-      ATT_TR_GROUP(0, 0)
-      ATT_TR_GROUP(1, 1)
-
-      // ---- mask + online softmax (all lane-local except one exchange with lane^32)
-      float mx = -INFINITY;
-      if (fast) {                   // every key of the tile is valid (all tiles but a ragged last one): no per-element mask
-        // four independent chains (max is exact: any order gives the same bits); one chain of 16 dependent v_max3 is a latency chain
-        float m4[4];
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-          const int kb = c4 >> 1, r0 = (c4 & 1) * 8;
-          m4[c4] = fmaxf(fmaxf(sacc[kb][r0], sacc[kb][r0 + 1]), sacc[kb][r0 + 2]);
-#pragma unroll
-          for (int r = 3; r < 8; ++r) m4[c4] = fmaxf(m4[c4], sacc[kb][r0 + r]);
-        }
-        mx = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-      } else {
-        const uint32_t wlo = (uint32_t)(word >> (4 * hi)), whi = (uint32_t)(word >> (32 + 4 * hi));
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          const uint32_t wsel = kb ? whi : wlo;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int kbit = (r & 3) + 8 * (r >> 2);  // key within the 32-block, minus 4*hi (already shifted)
-            const float s = ((wsel >> kbit) & 1u) ? sacc[kb][r] : -INFINITY;
-            sacc[kb][r] = s;
-            mx = fmaxf(mx, s);
-          }
-        }
-      }
-      {
-        // max over the two 32-lane halves through v_permlane32_swap (a VALU instruction): __shfl_xor is a ds_bpermute, an LDS-queue
-        // instruction whose lgkmcnt(0) also waits for the V reads requested in front of the softmax
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-        mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * scale_log2;      // scale > 0: max commutes with the scaling
-      }
-      const float m_new = fmaxf(m_run, mx);
-#if ATT_DEFER_MAX
-      // deferred rescale: a row keeps its old reference maximum as long as its maximum grows by less than 2^8 (P <= 256, exact in
-      // the bf16 exponent range; l and O stay consistent with m_run); when NO row of the wave has to move, the 64 accumulator
-      // multiplies + exp2 of the rescale are skipped.  The decision is per row (rows that stay multiply by exactly 1), so a row's
-      // result never depends on which other rows share its wave -- the packed and the padded layout stay bit-identical.
-      const bool grow = !(m_new - m_run <= 8.0f);                 // also true for m_run = -inf (first tile, or all keys masked so far)
-      if (__builtin_amdgcn_ballot_w64(grow) != 0ull) {
-        const float m_ref = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = grow ? __builtin_amdgcn_exp2f(m_run - m_ref) : 1.0f;  // m_run = -inf -> 0
-        m_run = grow ? m_new : m_run;
-        l_run *= alpha;
-#pragma unroll
-        for (int db = 0; db < 4; ++db)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[db][r] *= alpha;
-      }
-      const float m_use = (m_run == -INFINITY) ? 0.f : m_run;
-#else
-      const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);  // m_run = -inf -> 0
-      m_run = m_new;
-#endif
-      float psum = 0.f;
-      frag_t pb[2][2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          uint32_t pk[4];
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            // exp2(s*scale - m): one fma + one v_exp per score (masked scores are -inf -> 0)
-            const float p0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][8 * c + 2 * jj], scale_log2, -m_use));
-            const float p1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][8 * c + 2 * jj + 1], scale_log2, -m_use));
-            psum += p0 + p1;
-            pk[jj] = pack2_op<F16>(p0, p1);
-          }
-          pb[kb][c] = __builtin_bit_cast(frag_t, make_uint4(pk[0], pk[1], pk[2], pk[3]));
-        }
-#if ATT_DEFER_MAX
-      l_run += psum;
-#else
-      l_run = l_run * alpha + psum;
-#pragma unroll
-      for (int db = 0; db < 4; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[db][r] *= alpha;
-#endif
-
-
-      // ---- O^T += V^T P^T   (the four d-blocks are four independent accumulators: round-robin, never the same one twice in a row)
-      {
-#define ATT_TR_WAIT(N, BUF)                                                                                                           \
-  asm volatile("s_waitcnt lgkmcnt(" #N ")"                                                                                            \
-               : "+v"(vr[BUF][0][0]), "+v"(vr[BUF][0][1]), "+v"(vr[BUF][1][0]), "+v"(vr[BUF][1][1]), "+v"(vr[BUF][2][0]),              \
-                 "+v"(vr[BUF][2][1]), "+v"(vr[BUF][3][0]), "+v"(vr[BUF][3][1]))
-#define ATT_TR_MMA(G, BUF)                                                                                                            \
-  _Pragma("unroll") for (int db = 0; db < 4; ++db) {                                                                                  \
-    const s16x4_t v0 = vr[BUF][db][0], v1 = vr[BUF][db][1];                                                                           \
-    const frag_t vf = __builtin_bit_cast(frag_t, (__attribute__((ext_vector_type(8))) short){v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]}); \
-    oacc[db] = mma32(vf, pb[(G) >> 1][(G) & 1], oacc[db]);                                                                            \
-  }
-        ATT_TR_WAIT(8, 0);
-        ATT_TR_MMA(0, 0)
-        ATT_TR_GROUP(2, 0)
-        ATT_TR_WAIT(8, 1);
-        ATT_TR_MMA(1, 1)
-        ATT_TR_GROUP(3, 1)
-        ATT_TR_WAIT(8, 0);
-        ATT_TR_MMA(2, 0)
-        ATT_TR_WAIT(0, 1);
-        ATT_TR_MMA(3, 1)
-#undef ATT_TR_GROUP
-#undef ATT_TR_WAIT
-#undef ATT_TR_MMA
-      }
+      ATT_TILE_PV(v_lds)
     }
 
     // ---- block seam: the next block's first tile and Q rows (issued one tile ago) are waited for BEFORE this block's stores go out
@@ -522,61 +288,12 @@ attn_bidir_fwd_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ 
     if (more) q_read_half(1);
     ATT_STAMP();                                // block: seam wait done
 
-    // ---- epilogue: lane holds O[q][32db + 8g + 4hi + 0..3] in regs 4g..4g+3 of oacc[db]
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);     // (once per block; through v_permlane32_swap like the tile maximum: measured 2 % slower at S >= 2048)
-    const float inv_l = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-    // full-line stores through the transposition buffer (a row-per-lane store touches 32 lines x 32 B per instruction): one 64-column
-    // half at a time, every lane writes its 4 pieces of the half (unit ^= (row>>1)&7), then stores 16 B of an 8-row x 128-B piece
-    const int q_wave0 = qb * ATT_QB + wave * 32;
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    const int x_row = ln >> 3, x_unit = ln & 7;                                  // row (+ 8j) and physical unit of a store piece
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      char* wp = xs + (ln & 31) * 128;
-#pragma unroll
-      for (int dbl = 0; dbl < 2; ++dbl)
-#pragma unroll
-        for (int gp = 0; gp < 2; ++gp) {
-          // v_permlane32_swap exchanges the two 32-lane halves of the register groups g and g+1, so that a lane ends up with 8
-          // CONSECUTIVE dims of its row (half 0: group g, half 1: group g+1): one 16-byte piece
-          const int db = half * 2 + dbl;
-          float a[4], bq[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(oacc[db][8 * gp + e] * inv_l),
-                                                             __float_as_uint(oacc[db][8 * gp + 4 + e] * inv_l), false, false);
-            a[e] = __uint_as_float(sw[0]); bq[e] = __uint_as_float(sw[1]);
-          }
-          *reinterpret_cast<uint4*>(wp + (((dbl * 4 + gp * 2 + hi) ^ q_swz) << 4)) =
-              make_uint4(pack2_op<F16>(a[0], a[1]), pack2_op<F16>(a[2], a[3]), pack2_op<F16>(bq[0], bq[1]), pack2_op<F16>(bq[2], bq[3]));
-        }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);                                         // lgkmcnt(0): the wave's own writes are in the buffer
-      asm volatile("" ::: "memory");
-      uint4 piece[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) piece[j] = *reinterpret_cast<const uint4*>(xs + j * 1024 + ln * 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = 8 * j + x_row;
-        const int qr = q_wave0 + r;
+    // ---- epilogue (ATT_ABLATE_STORES: the stores are compiled but never executed)
 #ifdef ATT_ABLATE_STORES
-        if (qr < S && scale_log2 < -1e30f)
+    ATT_STORE_OUT(qb * ATT_QB + wave * 32, qr < S && scale_log2 < -1e30f, true)
 #else
-        if (qr < S)
+    ATT_STORE_OUT(qb * ATT_QB + wave * 32, qr < S, true)
 #endif
-        {
-          typedef __attribute__((ext_vector_type(4))) unsigned int att_u32x4_t;
-          att_u32x4_t* op = reinterpret_cast<att_u32x4_t*>(o_base + ((uint32_t)qr * out_stride_b + (uint32_t)((half * 8 + (x_unit ^ ((r >> 1) & 7))) << 4)));
-          const att_u32x4_t pv = {piece[j].x, piece[j].y, piece[j].z, piece[j].w};
-          *op = pv;
-        }
-      }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);                                         // the pieces are in registers before the buffer is reused
-      asm volatile("" ::: "memory");
-    }
     ATT_STAMP();                                // block: output stores issued
 #ifdef ATT_TIMING
     if (qi + 1 == nblk && tid == 0 && att_ns + 1 < att_cap) { att_st[att_ns++] = (uint32_t)__builtin_amdgcn_s_memrealtime(); att_st[att_ns++] = 0xffffffffu; }
@@ -594,20 +311,7 @@ attn_bidir_fwd_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ 
 
 using namespace grit;
 
-// Launch geometry: query blocks per workgroup (the K/V stream runs through the block seams, so more blocks per workgroup amortise the
-// prologue) -- as many as 4 while the launch still has >= 4 workgroups per CU-slot pair -- and the XCD-aware 1-D grid.
-// the 80 KiB dynamic-LDS opt-in is a per-device function attribute: set it once per (instantiation, device)
-template <typename KernelT>
-static void attn_lds_optin(KernelT kernel, std::atomic<uint64_t>& done, int bytes = ATT_LDS_BYTES) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done.fetch_or(bit, std::memory_order_release);
-  }
-}
-template <bool VARLEN, bool CAUSAL, bool F16 = false>
+template <bool VARLEN, bool CAUSAL, bool F16>
 static void attn_launch(dim3 grid, hipStream_t st, const uint16_t* qkv, const uint64_t* key_bits, const int32_t* cu, uint16_t* out, float* lse,
                         int S, int nq, int nkv, int64_t qkv_stride, int64_t out_stride, float scale_log2, int qpw, int ngx, int n_sets,
                         int window) {
@@ -617,6 +321,8 @@ static void attn_launch(dim3 grid, hipStream_t st, const uint16_t* qkv, const ui
                      out_stride, scale_log2, qpw, ngx, n_sets, window);
 }
 
+// Launch geometry: query blocks per workgroup (the K/V stream runs through the block seams, so more blocks per workgroup amortise the
+// prologue) -- as many as 4 while the launch still has >= 4 workgroups per CU-slot pair -- and the XCD-aware 1-D grid.
 struct AttnGeom {
   int qpw, ngx, n_sets;
   unsigned grid;
@@ -639,9 +345,11 @@ static AttnGeom attn_geom(int B, int max_len, int nq, int nkv, bool causal) {
   return g;
 }
 
-static int attn_fwd_padded(const char* name, bool causal, int window, const void* qkv, const uint64_t* key_bits, void* out, float* lse, int B, int S,
-                           int nq, int nkv, int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream, bool f16 = false) {
-  GRIT_REQUIRE(qkv && key_bits && out, GRIT_E_BADARG, "%s: null pointer", name);
+// Padded batches (varlen = false: S rows per sequence, key_bits) and packed ones (varlen = true: cu_seqlens, S = the longest sequence).
+static int attn_fwd(const char* name, bool varlen, bool causal, bool f16, int window, const void* qkv, const uint64_t* key_bits,
+                    const int32_t* cu_seqlens, void* out, float* lse, int B, int S, int nq, int nkv, int d, int64_t qkv_stride, int64_t out_stride,
+                    float scale, void* stream) {
+  GRIT_REQUIRE(qkv && (varlen ? (const void*)cu_seqlens : key_bits) && out, GRIT_E_BADARG, "%s: null pointer", name);
   GRIT_REQUIRE(B > 0 && S > 0 && nq > 0 && nkv > 0 && S <= (1 << 30) && nq <= 65535 && nkv <= 65535, GRIT_E_BADARG, "%s: bad sizes", name);
   GRIT_REQUIRE(d == ATT_D, GRIT_E_UNSUPPORTED, "%s: head_dim=%d (only 128 is built)", name, d);
   GRIT_REQUIRE(nq % nkv == 0, GRIT_E_BADARG, "%s: nq=%d not a multiple of nkv=%d", name, nq, nkv);
@@ -652,105 +360,72 @@ static int attn_fwd_padded(const char* name, bool causal, int window, const void
   GRIT_REQUIRE((int64_t)B * nq * ((S + ATT_QB - 1) / ATT_QB) < (1ll << 30), GRIT_E_UNSUPPORTED, "%s: grid too large", name);
   GRIT_REQUIRE((int64_t)S * qkv_stride * 2 < (1ll << 31) && (int64_t)S * out_stride * 2 < (1ll << 31), GRIT_E_UNSUPPORTED,
                "%s: one sequence spans more than 2 GiB (32-bit row offsets)", name);
+  typedef void (*launch_t)(dim3, hipStream_t, const uint16_t*, const uint64_t*, const int32_t*, uint16_t*, float*, int, int, int, int64_t,
+                           int64_t, float, int, int, int, int);
+  static const launch_t launch[2][2][2] = {      // [varlen][!causal][!f16]
+      {{attn_launch<false, true, true>, attn_launch<false, true, false>}, {attn_launch<false, false, true>, attn_launch<false, false, false>}},
+      {{attn_launch<true, true, true>, attn_launch<true, true, false>}, {attn_launch<true, false, true>, attn_launch<true, false, false>}}};
   const AttnGeom g = attn_geom(B, S, nq, nkv, causal);
-  const dim3 grid(g.grid);
-  if (causal && f16)
-    attn_launch<false, true, true>(grid, (hipStream_t)stream, (const uint16_t*)qkv, key_bits, nullptr, (uint16_t*)out, lse, S, nq, nkv, qkv_stride,
-                                   out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, window);
-  else if (causal)
-    attn_launch<false, true>(grid, (hipStream_t)stream, (const uint16_t*)qkv, key_bits, nullptr, (uint16_t*)out, lse, S, nq, nkv, qkv_stride,
-                             out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, causal ? window : 0);
-  else if (f16)
-    attn_launch<false, false, true>(grid, (hipStream_t)stream, (const uint16_t*)qkv, key_bits, nullptr, (uint16_t*)out, lse, S, nq, nkv, qkv_stride,
-                                    out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, 0);
-  else
-    attn_launch<false, false>(grid, (hipStream_t)stream, (const uint16_t*)qkv, key_bits, nullptr, (uint16_t*)out, lse, S, nq, nkv, qkv_stride,
-                              out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, causal ? window : 0);
-  GRIT_CHECK_LAUNCH(name);
-  return GRIT_OK;
-}
-
-static int attn_fwd_varlen(const char* name, bool causal, int window, const void* qkv, const int32_t* cu_seqlens, void* out, float* lse, int B, int max_len,
-                           int nq, int nkv, int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream, bool f16 = false) {
-  GRIT_REQUIRE(qkv && cu_seqlens && out, GRIT_E_BADARG, "%s: null pointer", name);
-  GRIT_REQUIRE(B > 0 && max_len > 0 && nq > 0 && nkv > 0 && max_len <= (1 << 30) && nq <= 65535 && nkv <= 65535, GRIT_E_BADARG, "%s: bad sizes", name);
-  GRIT_REQUIRE(d == ATT_D, GRIT_E_UNSUPPORTED, "%s: head_dim=%d (only 128 is built)", name, d);
-  GRIT_REQUIRE(nq % nkv == 0, GRIT_E_BADARG, "%s: nq=%d not a multiple of nkv=%d", name, nq, nkv);
-  GRIT_REQUIRE(window >= 0 && (causal || window == 0), GRIT_E_BADARG, "%s: window=%d (>= 1 keys per query, causal attention only)", name, window);
-  GRIT_REQUIRE(qkv_stride % 8 == 0 && qkv_stride >= (int64_t)(nq + 2 * nkv) * d && out_stride % 8 == 0 && out_stride >= (int64_t)nq * d,
-               GRIT_E_BADARG, "%s: bad strides", name);
-  GRIT_REQUIRE(aligned16(qkv) && aligned16(out), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", name);
-  GRIT_REQUIRE((int64_t)B * nq * ((max_len + ATT_QB - 1) / ATT_QB) < (1ll << 30), GRIT_E_UNSUPPORTED, "%s: grid too large", name);
-  GRIT_REQUIRE((int64_t)max_len * qkv_stride * 2 < (1ll << 31) && (int64_t)max_len * out_stride * 2 < (1ll << 31), GRIT_E_UNSUPPORTED,
-               "%s: one sequence spans more than 2 GiB (32-bit row offsets)", name);
-  const AttnGeom g = attn_geom(B, max_len, nq, nkv, causal);
-  const dim3 grid(g.grid);
-  if (causal && f16)
-    attn_launch<true, true, true>(grid, (hipStream_t)stream, (const uint16_t*)qkv, nullptr, cu_seqlens, (uint16_t*)out, lse, max_len, nq, nkv, qkv_stride,
-                                  out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, window);
-  else if (causal)
-    attn_launch<true, true>(grid, (hipStream_t)stream, (const uint16_t*)qkv, nullptr, cu_seqlens, (uint16_t*)out, lse, max_len, nq, nkv, qkv_stride,
-                            out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, causal ? window : 0);
-  else if (f16)
-    attn_launch<true, false, true>(grid, (hipStream_t)stream, (const uint16_t*)qkv, nullptr, cu_seqlens, (uint16_t*)out, lse, max_len, nq, nkv, qkv_stride,
-                                   out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, 0);
-  else
-    attn_launch<true, false>(grid, (hipStream_t)stream, (const uint16_t*)qkv, nullptr, cu_seqlens, (uint16_t*)out, lse, max_len, nq, nkv, qkv_stride,
-                             out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, causal ? window : 0);
+  launch[varlen][!causal][!f16](dim3(g.grid), (hipStream_t)stream, (const uint16_t*)qkv, key_bits, cu_seqlens, (uint16_t*)out, lse, S, nq, nkv,
+                              qkv_stride, out_stride, scale * 1.4426950408889634f, g.qpw, g.ngx, g.n_sets, window);
   GRIT_CHECK_LAUNCH(name);
   return GRIT_OK;
 }
 
 extern "C" int grit_attn_bidir_fwd(const void* qkv, const uint64_t* key_bits, void* out, float* lse, int B, int S, int nq, int nkv,
                                    int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_fwd_padded("grit_attn_bidir_fwd", false, 0, qkv, key_bits, out, lse, B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
+  return attn_fwd("grit_attn_bidir_fwd", false, false, false, 0, qkv, key_bits, nullptr, out, lse, 
+                  B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 // fp16-operand policy: qkv and out hold IEEE fp16.  Bidirectional (the embedding path) and -- ABI 5 -- causal, optionally with a sliding
 // window of `window` keys (0: none): the causal prompt pass of a unified / generative model and the 'cc' embedding attention
 extern "C" int grit_attn_causal_f16_fwd(const void* qkv, const uint64_t* key_bits, void* out, float* lse, int B, int S, int nq, int nkv,
                                         int d, int64_t qkv_stride, int64_t out_stride, float scale, int window, void* stream) {
-  return attn_fwd_padded("grit_attn_causal_f16_fwd", true, window, qkv, key_bits, out, lse, B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream, true);
+  return attn_fwd("grit_attn_causal_f16_fwd", false, true, true, window, qkv, key_bits, nullptr, out, lse, 
+                  B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_causal_varlen_f16_fwd(const void* qkv, const int32_t* cu_seqlens, void* out, float* lse, int B, int max_len, int nq,
                                                int nkv, int d, int64_t qkv_stride, int64_t out_stride, float scale, int window, void* stream) {
-  return attn_fwd_varlen("grit_attn_causal_varlen_f16_fwd", true, window, qkv, cu_seqlens, out, lse, B, max_len, nq, nkv, d, qkv_stride, out_stride,
-                         scale, stream, true);
+  return attn_fwd("grit_attn_causal_varlen_f16_fwd", true, true, true, window, qkv, nullptr, cu_seqlens, out, lse, 
+                  B, max_len, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_bidir_f16_fwd(const void* qkv, const uint64_t* key_bits, void* out, float* lse, int B, int S, int nq, int nkv,
                                        int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_fwd_padded("grit_attn_bidir_f16_fwd", false, 0, qkv, key_bits, out, lse, B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream, true);
+  return attn_fwd("grit_attn_bidir_f16_fwd", false, false, true, 0, qkv, key_bits, nullptr, out, lse, 
+                  B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_bidir_varlen_f16_fwd(const void* qkv, const int32_t* cu_seqlens, void* out, float* lse, int B, int max_len, int nq,
                                               int nkv, int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_fwd_varlen("grit_attn_bidir_varlen_f16_fwd", false, 0, qkv, cu_seqlens, out, lse, B, max_len, nq, nkv, d, qkv_stride, out_stride, scale,
-                         stream, true);
+  return attn_fwd("grit_attn_bidir_varlen_f16_fwd", true, false, true, 0, qkv, nullptr, cu_seqlens, out, lse, 
+                  B, max_len, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_causal_fwd(const void* qkv, const uint64_t* key_bits, void* out, float* lse, int B, int S, int nq, int nkv,
                                     int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_fwd_padded("grit_attn_causal_fwd", true, 0, qkv, key_bits, out, lse, B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
+  return attn_fwd("grit_attn_causal_fwd", false, true, false, 0, qkv, key_bits, nullptr, out, lse, 
+                  B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_bidir_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, void* out, float* lse, int B, int max_len, int nq,
                                           int nkv, int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_fwd_varlen("grit_attn_bidir_varlen_fwd", false, 0, qkv, cu_seqlens, out, lse, B, max_len, nq, nkv, d, qkv_stride, out_stride, scale,
-                         stream);
+  return attn_fwd("grit_attn_bidir_varlen_fwd", true, false, false, 0, qkv, nullptr, cu_seqlens, out, lse, 
+                  B, max_len, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_causal_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, void* out, float* lse, int B, int max_len, int nq,
                                            int nkv, int d, int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_fwd_varlen("grit_attn_causal_varlen_fwd", true, 0, qkv, cu_seqlens, out, lse, B, max_len, nq, nkv, d, qkv_stride, out_stride, scale,
-                         stream);
+  return attn_fwd("grit_attn_causal_varlen_fwd", true, true, false, 0, qkv, nullptr, cu_seqlens, out, lse, 
+                  B, max_len, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 
 // Sliding-window causal attention: query q sees keys q - window + 1 .. q (window >= 1; window >= S is plain causal attention).
 extern "C" int grit_attn_causal_window_fwd(const void* qkv, const uint64_t* key_bits, void* out, float* lse, int B, int S, int nq, int nkv,
                                            int d, int64_t qkv_stride, int64_t out_stride, float scale, int window, void* stream) {
   GRIT_REQUIRE(window >= 1, GRIT_E_BADARG, "grit_attn_causal_window_fwd: window=%d must be >= 1", window);
-  return attn_fwd_padded("grit_attn_causal_window_fwd", true, window, qkv, key_bits, out, lse, B, S, nq, nkv, d, qkv_stride, out_stride, scale,
-                         stream);
+  return attn_fwd("grit_attn_causal_window_fwd", false, true, false, window, qkv, key_bits, nullptr, out, lse, 
+                  B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_causal_window_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, void* out, float* lse, int B, int max_len, int nq,
                                                   int nkv, int d, int64_t qkv_stride, int64_t out_stride, float scale, int window,
                                                   void* stream) {
   GRIT_REQUIRE(window >= 1, GRIT_E_BADARG, "grit_attn_causal_window_varlen_fwd: window=%d must be >= 1", window);
-  return attn_fwd_varlen("grit_attn_causal_window_varlen_fwd", true, window, qkv, cu_seqlens, out, lse, B, max_len, nq, nkv, d, qkv_stride,
-                         out_stride, scale, stream);
+  return attn_fwd("grit_attn_causal_window_varlen_fwd", true, true, false, window, qkv, nullptr, cu_seqlens, out, lse, 
+                  B, max_len, nq, nkv, d, qkv_stride, out_stride, scale, stream);
 }
