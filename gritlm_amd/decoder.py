@@ -4,7 +4,13 @@ Replaces, for the RAG doc-caching flow of the reference (rag/eval.py:237-302: ``
 ``kv_cache`` came from ``encode(..., get_cache=True)``, gritlm/gritlm.py:131-140), the Hugging Face decode loop: every projection of a
 decode step is an HBM-bound GEMV (``grit_gemv_bf16``), attention reads the sequence's KV once (``grit_attn_decode``), the new token's
 K/V are appended in place, sampling is a device-side argmax -- and the whole step (5 launches per layer) is captured in ONE HIP
-graph, so the host only replays it.  Greedy decoding only (``do_sample=False``), batch <= 8, head_dim 128.
+graph, so the host only replays it.  Greedy decoding only (``do_sample=False``), head_dim 128.
+
+Batch: 1 to 64 sequences (sparse-MoE engines: 1 to 8).  At 1..8 rows every projection of a step is the GEMV above; at 9..64 rows it is
+the MFMA decode GEMM (``grit_decode_gemm_*`` / ``grit_rmsnorm_decode_gemm_*_deferred``: every weight element read once per step whatever
+the row count), the other kernels of the step are the same, and the step is still one graph.  The seam at 8 | 9: a row decoded in a batch
+of 8 and the same row in a batch of 9 differ in the last bits (GEMV against MFMA summation order, and the deferred norm's operand
+x * ln_w is rounded once to the 16-bit operand format on the MFMA); within 9..64 a row's bits do not depend on the batch.
 
 Precision (round 6): the decoder follows its engine's policy.  Under ``"bf16"`` / ``"fp32_residual"`` the step is the reference's bf16
 arithmetic (teacher-forced logits within ~1e-3 (1 - cos) of the fp32 module: the bf16 level).  Under ``"f16_operands"`` / ``"f16_stream"`` it
@@ -16,7 +22,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from ._lib import EPI_RESIDUAL, EPI_SWIGLU
+from ._lib import EPI_RESIDUAL, EPI_STORE, EPI_SWIGLU
 from ._lib import GritHipError
 from .encoder import F16_POLICIES, MistralEncoderEngine, rope_tables
 
@@ -24,6 +30,20 @@ BF16, F16, F32, I32, I64 = torch.bfloat16, torch.float16, torch.float32, torch.i
 
 
 PREFILL_MODES = ("rows", "gemm")
+GEMV_ROWS = 8           # up to this many rows a step's projections are GEMVs (grit_gemv_*); above, the MFMA decode GEMMs
+MAX_ROWS = 64           # the batch limit of the dense decoder (grit_decode_gemm_*: 1..64 rows)
+
+
+def _proj(x: torch.Tensor, w: torch.Tensor, **kw):
+    """x @ w^T of a decode step (epilogues of ops.gemv): the GEMV at 1..8 rows, the MFMA decode GEMM at 9..64."""
+    return (ops.gemv if x.shape[0] <= GEMV_ROWS else ops.decode_gemm)(x, w, **kw)
+
+
+def _norm_proj(x: torch.Tensor, ln_w: torch.Tensor, eps: float, w: torch.Tensor, out: torch.Tensor, epilogue: int = EPI_STORE):
+    """the deferred RMSNorm + projection of a decode step: rmsnorm_gemv(deferred) at 1..8 rows, rmsnorm_decode_gemm at 9..64"""
+    if x.shape[0] <= GEMV_ROWS:
+        return ops.rmsnorm_gemv(x, ln_w, eps, w, out=out, epilogue=epilogue, deferred=True)
+    return ops.rmsnorm_decode_gemm(x, ln_w, eps, w, out=out, epilogue=epilogue)
 
 
 def prefill_layout(attention_mask: torch.Tensor, lens: torch.Tensor, Lmax: int | None = None):
@@ -119,12 +139,12 @@ class MistralDecoder:
         for li, L in enumerate(e.layers):
             wqkv, wo, wgu, wdown = e._f16_weights(L)
             ck, cv = st["cache"][li]
-            ops.rmsnorm_gemv(h16, L.ln1, eps, wqkv, out=qkv, deferred=True)
+            _norm_proj(h16, L.ln1, eps, wqkv, qkv)
             ops.attn_decode_rope(qkv, st["cos"], st["sin"], ck, cv, st["lens"], ctx, st["ws"], nq, nkv, d)
-            ops.gemv(ctx, wo, out=h, epilogue=EPI_RESIDUAL, residual=h, out16=h16)
-            ops.rmsnorm_gemv(h16, L.ln2, eps, wgu, out=act, epilogue=EPI_SWIGLU, deferred=True)
-            ops.gemv(act, wdown, out=h, epilogue=EPI_RESIDUAL, residual=h, out16=h16)
-        ops.rmsnorm_gemv(h16, e.norm, eps, self._lm_head_f16(), out=st["logits"], deferred=True)
+            _proj(ctx, wo, out=h, epilogue=EPI_RESIDUAL, residual=h, out16=h16)
+            _norm_proj(h16, L.ln2, eps, wgu, act, epilogue=EPI_SWIGLU)
+            _proj(act, wdown, out=h, epilogue=EPI_RESIDUAL, residual=h, out16=h16)
+        _norm_proj(h16, e.norm, eps, self._lm_head_f16(), st["logits"])
 
     def _step_moe(self, st):
         """One decode step of a sparse-MoE (Mixtral) model, MixtralSparseMoeBlock.forward (scripts/modeling_mixtral_gritlm.py:839-882) at 1..8
@@ -187,40 +207,52 @@ class MistralDecoder:
         dm = self.fuse_norm in ("deferred", "deferred_mlp")           # MLP / final norm in the deferred form
         dq = self.fuse_norm == "deferred"                              # q|k|v norm as well
         fuse_mlp = dm or self.fuse_norm == "all"
+        big = h.shape[0] > GEMV_ROWS                                   # 9..64 rows: the MFMA decode GEMMs (deferred forms only)
         for li, L in enumerate(e.layers):
             ck, cv = st["cache"][li]
-            ops.rmsnorm_gemv(h, L.ln1, eps, L.wqkv, out=qkv, deferred=dq)         # input_layernorm + q/k/v projections
+            if big and not dq:                                         # ("deferred_mlp": the exact q|k|v norm gets its own launch)
+                ops.rmsnorm(h, L.ln1, eps, out=st["x"])
+                ops.decode_gemm(st["x"], L.wqkv, out=qkv)
+            elif big:
+                ops.rmsnorm_decode_gemm(h, L.ln1, eps, L.wqkv, out=qkv)
+            else:
+                ops.rmsnorm_gemv(h, L.ln1, eps, L.wqkv, out=qkv, deferred=dq)         # input_layernorm + q/k/v projections
             ops.attn_decode_rope(qkv, st["cos"], st["sin"], ck, cv, st["lens"], ctx, st["ws"], nq, nkv, d)   # RoPE + KV append + attention
-            ops.gemv(ctx, L.wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
-            if fuse_mlp:
+            _proj(ctx, L.wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
+            if fuse_mlp and big:
+                ops.rmsnorm_decode_gemm(h, L.ln2, eps, L.wgu, out=act, epilogue=EPI_SWIGLU)
+            elif fuse_mlp:
                 ops.rmsnorm_gemv(h, L.ln2, eps, L.wgu, out=act, epilogue=EPI_SWIGLU, deferred=dm)   # post_attention_layernorm + gate/up + SwiGLU
             else:
                 ops.rmsnorm(h, L.ln2, eps, out=st["x"])
                 ops.gemv(st["x"], L.wgu, out=act, epilogue=EPI_SWIGLU)
-            ops.gemv(act, L.wdown, out=h, epilogue=EPI_RESIDUAL, residual=h)
-        if fuse_mlp:
+            _proj(act, L.wdown, out=h, epilogue=EPI_RESIDUAL, residual=h)
+        if fuse_mlp and big:
+            ops.rmsnorm_decode_gemm(h, e.norm, eps, self.lm_head, out=st["logits"])
+        elif fuse_mlp:
             ops.rmsnorm_gemv(h, e.norm, eps, self.lm_head, out=st["logits"], deferred=dm)       # final norm + lm_head
         else:
             ops.rmsnorm(h, e.norm, eps, out=st["x"])
             ops.gemv(st["x"], self.lm_head, out=st["logits"])
 
     def _step_unfused_norm(self, st):
-        """More than 2 rows: every workgroup of the fused kernel would re-derive each row's RMS, so the norm gets its own launch."""
+        """More than 2 rows: every workgroup of the fused kernel would re-derive each row's RMS, so the norm gets its own launch (the exact
+        forms "qkv" / "all" / "none"; above 8 rows the projections are the MFMA decode GEMMs)."""
         c, e = self.cfg, self.eng
         nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
         h, x, qkv, ctx, act = st["h"], st["x"], st["qkv"], st["ctx"], st["act"]
         for li, L in enumerate(e.layers):
             ck, cv = st["cache"][li]
             ops.rmsnorm(h, L.ln1, eps, out=x)
-            ops.gemv(x, L.wqkv, out=qkv)
+            _proj(x, L.wqkv, out=qkv)
             ops.rope_kv_append(qkv, st["cos"], st["sin"], ck, cv, st["lens"], nq, nkv, d)
             ops.attn_decode(qkv, ck, cv, st["lens"], ctx, st["ws"], nq, nkv, d)
-            ops.gemv(ctx, L.wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
+            _proj(ctx, L.wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
             ops.rmsnorm(h, L.ln2, eps, out=x)
-            ops.gemv(x, L.wgu, out=act, epilogue=EPI_SWIGLU)
-            ops.gemv(act, L.wdown, out=h, epilogue=EPI_RESIDUAL, residual=h)
+            _proj(x, L.wgu, out=act, epilogue=EPI_SWIGLU)
+            _proj(act, L.wdown, out=h, epilogue=EPI_RESIDUAL, residual=h)
         ops.rmsnorm(h, e.norm, eps, out=x)
-        ops.gemv(x, self.lm_head, out=st["logits"])
+        _proj(x, self.lm_head, out=st["logits"])
 
     # ------------------------------------------------------------------ a prompt chunk on top of the cache, all its tokens at once
     def _prompt_rows(self, st, ids: torch.Tensor):
@@ -267,7 +299,7 @@ class MistralDecoder:
                 else:
                     ops.gemv(act[a:b], wdown, out=h[a:b], epilogue=EPI_RESIDUAL, residual=h[a:b])
         last = x_in.view(B, P, -1)[:, P - 1].contiguous()                  # the stream of every sequence's last prompt token
-        ops.rmsnorm_gemv(last, e.norm, eps, self._lm_head_f16() if f16 else self.lm_head, out=st["logits"], deferred=True)
+        _norm_proj(last, e.norm, eps, self._lm_head_f16() if f16 else self.lm_head, st["logits"])             # (B rows: 9..64 on the MFMA)
         st["lens"] += P
 
     def _prompt_gemm(self, st, ids: torch.Tensor, mask: torch.Tensor):
@@ -289,9 +321,9 @@ class MistralDecoder:
         finally:
             e.precision = pol
         if f16:
-            ops.rmsnorm_gemv(hl.to(F16), e.norm, c.rms_norm_eps, self._lm_head_f16(), out=st["logits"], deferred=True)
+            _norm_proj(hl.to(F16), e.norm, c.rms_norm_eps, self._lm_head_f16(), st["logits"])
         else:
-            ops.gemv(hl, self.lm_head, out=st["logits"])
+            _proj(hl, self.lm_head, out=st["logits"])
         st["lens"] += plen
 
     def _sample(self, st):
@@ -334,6 +366,11 @@ class MistralDecoder:
         dev, c = self.device, self.cfg
         if self.prefill not in PREFILL_MODES:
             raise ValueError(f"MistralDecoder.prefill={self.prefill!r}: one of {PREFILL_MODES}")
+        B = input_ids.shape[0]
+        if B > MAX_ROWS:
+            raise NotImplementedError(f"native decode: batch <= {MAX_ROWS} (got {B}); split the batch")
+        if self.moe and B > GEMV_ROWS:
+            raise NotImplementedError(f"native decode of a sparse-MoE (Mixtral) engine: batch <= {GEMV_ROWS} (got {B})")
         f16 = self._f16() and not _force_bf16
         on_overflow = self.on_overflow if on_overflow is None else on_overflow
         if on_overflow not in ("raise", "bf16"):
@@ -343,8 +380,6 @@ class MistralDecoder:
             self.eng._f16_weights(self.eng.layers[0])     # (refuses weights beyond the fp16 range before anything runs)
         ids = input_ids.to(device=dev, dtype=I64)
         B, P = ids.shape
-        if B > 8:
-            raise NotImplementedError("native decode: batch <= 8")
         nq, nkv, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         past = _layers_of(past_key_values) if past_key_values is not None else None
         S0 = past[0][0].shape[2] if past is not None else 0
@@ -381,9 +416,9 @@ class MistralDecoder:
             self.last_prefill = "encoder"
             last = hidden[torch.arange(B, device=dev), (plen - 1).long()].contiguous()              # [B,H] of the last prompt token
             if f16:
-                ops.rmsnorm_gemv(last.to(F16), self.eng.norm, c.rms_norm_eps, self._lm_head_f16(), out=st["logits"], deferred=True)
+                _norm_proj(last.to(F16), self.eng.norm, c.rms_norm_eps, self._lm_head_f16(), st["logits"])
             else:
-                ops.gemv(last, self.lm_head, out=st["logits"])                                       # (final-norm output, bf16)
+                _proj(last, self.lm_head, out=st["logits"])                                          # (final-norm output, bf16)
         elif self.prefill == "gemm" and P > 0:
             mask = torch.ones((B, P), dtype=I64, device=dev) if attention_mask is None else attention_mask.to(device=dev, dtype=I64)
             prefill_layout(mask, torch.zeros((B,), dtype=I32, device=dev))        # (refuses a mask that is not right-padded before anything runs)

@@ -702,6 +702,48 @@ def rmsnorm_gemv(x: torch.Tensor, ln_w: torch.Tensor, eps: float, w: torch.Tenso
     return out
 
 
+def decode_gemm(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None, epilogue: int = EPI_STORE,
+                residual: torch.Tensor | None = None, out16: torch.Tensor | None = None) -> torch.Tensor:
+    """out[B,N] = x[B,K] @ w[N,K]^T for 1..64 rows on the MFMA (batched decode: the step's projections above 8 rows); the epilogues and
+    formats of ``gemv`` (fp16 ``w``: STORE / RESIDUAL write fp32, ``out16`` the fp16 copy, SWIGLU the fp16 activation).  A row's output
+    does not depend on B or on the other rows, bit for bit; it differs from ``gemv``'s in the last bits (another summation order)."""
+    B, K = x.shape
+    N = w.shape[0]
+    n_out = N // 2 if epilogue == EPI_SWIGLU else N
+    if w.dtype == F16:
+        odt = F16 if epilogue == EPI_SWIGLU else F32
+        if out is None:
+            out = torch.empty((B, n_out), dtype=odt, device=x.device)
+        check(_lib.load().grit_decode_gemm_f16(_chk2d(x, F16, "x"), _chk2d(w, F16, "w"), _chk2d(out, odt, "out"), B, N, K, x.stride(0),
+                                               w.stride(0), out.stride(0), epilogue, 0 if residual is None else _chk2d(residual, F32, "residual"),
+                                               0 if residual is None else residual.stride(0), 0 if out16 is None else _chk2d(out16, F16, "out16"),
+                                               0 if out16 is None else out16.stride(0), _stream()), "grit_decode_gemm_f16")
+        return out
+    if out is None:
+        out = torch.empty((B, n_out), dtype=BF16, device=x.device)
+    check(_lib.load().grit_decode_gemm_bf16(_chk2d(x, BF16, "x"), _chk2d(w, BF16, "w"), _chk2d(out, BF16, "out"), B, N, K, x.stride(0),
+                                            w.stride(0), out.stride(0), epilogue, 0 if residual is None else _chk2d(residual, BF16, "residual"),
+                                            0 if residual is None else residual.stride(0), _stream()), "grit_decode_gemm_bf16")
+    return out
+
+
+def rmsnorm_decode_gemm(x: torch.Tensor, ln_w: torch.Tensor, eps: float, w: torch.Tensor, out: torch.Tensor | None = None,
+                        epilogue: int = EPI_STORE) -> torch.Tensor:
+    """decode_gemm with the DEFERRED RMSNorm of x folded in (the row scale multiplies the finished fp32 sums; x * ln_w is rounded once to
+    the operand format for the MFMA).  1..64 rows; STORE or SWIGLU; fp16 ``w``: x is the fp16 copy of the stream, STORE writes fp32."""
+    B, K = x.shape
+    N = w.shape[0]
+    n_out = N // 2 if epilogue == EPI_SWIGLU else N
+    f16 = w.dtype == F16
+    odt = (F16 if epilogue == EPI_SWIGLU else F32) if f16 else BF16
+    if out is None:
+        out = torch.empty((B, n_out), dtype=odt, device=x.device)
+    fn = _lib.load().grit_rmsnorm_decode_gemm_f16_deferred if f16 else _lib.load().grit_rmsnorm_decode_gemm_bf16_deferred
+    check(fn(_chk2d(x, F16 if f16 else BF16, "x"), _chk(ln_w, BF16, "ln_w"), float(eps), _chk2d(w, F16 if f16 else BF16, "w"),
+             _chk2d(out, odt, "out"), B, N, K, x.stride(0), w.stride(0), out.stride(0), epilogue, _stream()), "grit_rmsnorm_decode_gemm")
+    return out
+
+
 def rope_kv_append(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, lens: torch.Tensor,
                    nq: int, nkv: int, d: int):
     B, _, Lmax, _ = cache_k.shape

@@ -460,6 +460,27 @@ int grit_attn_decode_rope_f16(const void* qkv, const float* cos_tab, const float
 int grit_argmax_advance_f32(const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history,
                             int64_t hist_stride, int32_t* step, int B, void* stream);
 
+/* Batched decode (the native decoder at 9..64 rows; what model.generate does for a batch, rag/eval.py:296-302): out[b,:] = x[b,:] W^T for
+ * B = 1..64 rows on the MFMA (csrc/decode_gemm.hip), every weight element read once per launch.  Same arguments, epilogues, formats and
+ * rounding points as grit_gemv_bf16 / grit_gemv_f16 / grit_rmsnorm_gemv_{bf16,f16}_deferred (STORE, RESIDUAL -- in place with
+ * out == residual --, SWIGLU; fp16: fp32 STORE / RESIDUAL, the optional fp16 copy out16, fp16 SWIGLU, overflow flag).  Accumulation in
+ * fp32, summed in a fixed order (no atomics): bit-reproducible, and a row's output depends on that row's inputs, N and K only -- not on
+ * B or on the other rows.  The summation order differs from the GEMV's: the same row through the GEMV and through these kernels differs
+ * in the last bits.  Rows >= B and columns N .. ldo-1 are never written.
+ * The deferred-norm forms: out = rsqrt(mean x^2 + eps) * (W (x * ln_weight)), the sum of squares from the x rows the kernel stages for
+ * the product; the MFMA takes a 16-bit operand, so x * ln_weight is rounded ONCE to bf16 / fp16 (the GEMV's deferred form keeps it in
+ * fp32; the reference rounds x_n twice, modeling_mistral_gritlm.py:84-89).  Epilogues STORE and SWIGLU.
+ * Limits: B in 1..64, K % 64 == 0, N % 16 == 0 (SWIGLU: N % 32 == 0), otherwise GRIT_E_UNSUPPORTED; null pointers, ldx / ldw not >= K
+ * and multiples of 8, x / W / ln_weight not 16-byte aligned, short ldo / ldr / ldo16, an unknown epilogue: GRIT_E_BADARG.  No launch then. */
+int grit_decode_gemm_bf16(const void* x, const void* W, void* out, int B, int N, int K, int64_t ldx, int64_t ldw, int64_t ldo,
+                          int epilogue, const void* residual, int64_t ldr, void* stream);
+int grit_decode_gemm_f16(const void* x, const void* W, void* out, int B, int N, int K, int64_t ldx, int64_t ldw, int64_t ldo,
+                         int epilogue, const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream);
+int grit_rmsnorm_decode_gemm_bf16_deferred(const void* x, const void* ln_weight, float eps, const void* W, void* out, int B, int N, int K,
+                                           int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream);
+int grit_rmsnorm_decode_gemm_f16_deferred(const void* x, const void* ln_weight, float eps, const void* W, void* out, int B, int N, int K,
+                                          int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream);
+
 /* Sparse-MoE decode (ABI 5; E since ABI 6; MixtralSparseMoeBlock.forward, scripts/modeling_mixtral_gritlm.py:839-882, at 1..8 rows): x [B,K]
  * times ONE matrix of the stack W [E,N,K] -- matrix expert[0], an int32 in DEVICE memory (the router's choice for the row, so that the decode
  * step stays one HIP graph); w_expert_stride = elements between consecutive matrices, E >= 1 the number of matrices: the kernel clamps
