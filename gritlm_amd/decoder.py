@@ -4,7 +4,8 @@ Replaces, for the RAG doc-caching flow of the reference (rag/eval.py:237-302: ``
 ``kv_cache`` came from ``encode(..., get_cache=True)``, gritlm/gritlm.py:131-140), the Hugging Face decode loop: every projection of a
 decode step is an HBM-bound GEMV (``grit_gemv_bf16``), attention reads the sequence's KV once (``grit_attn_decode``), the new token's
 K/V are appended in place, sampling is a device-side argmax -- and the whole step (5 launches per layer) is captured in ONE HIP
-graph, so the host only replays it.  Greedy decoding only (``do_sample=False``), head_dim 128.
+graph, so the host only replays it.  Greedy by default; ``do_sample=True`` draws each token with temperature / top-k / top-p on the device
+(``grit_sample_advance``: one launch in place of the argmax, the step is still one graph).  head_dim 128.
 
 Batch: 1 to 64 sequences (sparse-MoE engines: 1 to 8).  At 1..8 rows every projection of a step is the GEMV above; at 9..64 rows it is
 the MFMA decode GEMM (``grit_decode_gemm_*`` / ``grit_rmsnorm_decode_gemm_*_deferred``: every weight element read once per step whatever
@@ -19,6 +20,9 @@ continuation of ``encode(get_cache=True)`` at the north-star's own level (fp16 K
 """
 from __future__ import annotations
 
+import math
+import numbers
+
 import torch
 
 from . import ops
@@ -32,6 +36,35 @@ BF16, F16, F32, I32, I64 = torch.bfloat16, torch.float16, torch.float32, torch.i
 PREFILL_MODES = ("rows", "gemm")
 GEMV_ROWS = 8           # up to this many rows a step's projections are GEMVs (grit_gemv_*); above, the MFMA decode GEMMs
 MAX_ROWS = 64           # the batch limit of the dense decoder (grit_decode_gemm_*: 1..64 rows)
+
+
+def check_sampling(temperature, top_k, top_p, num_return_sequences, do_sample: bool = True):
+    """The sampling parameters of generate(), refused before anything runs: T > 0 and finite, integer top_k >= 0, 0 <= top_p <= 1, integer
+    num_return_sequences >= 1 (above 1 only when sampling: greedy copies of a prompt would be identical, and Hugging Face refuses them)."""
+    if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, numbers.Integral) or num_return_sequences < 1:
+        raise ValueError(f"num_return_sequences={num_return_sequences!r}: an integer >= 1")
+    if not do_sample:
+        if num_return_sequences != 1:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True")
+        return
+    if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or top_k < 0:
+        raise ValueError(f"top_k={top_k!r}: an integer >= 0 (0: no top-k filter)")
+    if not (isinstance(temperature, numbers.Real) and math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"temperature={temperature!r}: a finite number > 0")
+    if not (isinstance(top_p, numbers.Real) and 0.0 <= top_p <= 1.0):
+        raise ValueError(f"top_p={top_p!r}: a number in [0, 1]")
+
+
+def row_keys(seed: int, rows: int, device) -> torch.Tensor:
+    """The RNG keys of a call's rows: key_r = seed + r (mod 2^64), as the int64 bit patterns grit_sample_advance reads as uint64."""
+    ks = [(int(seed) + r) % 2 ** 64 for r in range(rows)]
+    return torch.tensor([k - 2 ** 64 if k >= 2 ** 63 else k for k in ks], dtype=I64, device=device)
+
+
+def draw_seed() -> int:
+    """A 64-bit seed from torch's default CPU generator (torch.manual_seed / transformers.set_seed reproduce it)."""
+    lo, hi = (int(x) for x in torch.randint(0, 2 ** 32, (2,), dtype=torch.int64))
+    return (hi << 32) | lo
 
 
 def _proj(x: torch.Tensor, w: torch.Tensor, **kw):
@@ -326,8 +359,14 @@ class MistralDecoder:
             _proj(hl, self.lm_head, out=st["logits"])
         st["lens"] += plen
 
-    def _sample(self, st):
-        ops.argmax_advance(st["logits"], st["next"], st["lens"], st["history"], st["step"])
+    def _sample(self, st, lens: bool = True):
+        """the token of the step: the device argmax, or with st["sampling"] = (T, top_k, top_p) the sampled draw on the rows' keys"""
+        ln = st["lens"] if lens else None
+        if st.get("sampling") is not None:
+            T, k, p = st["sampling"]
+            ops.sample_advance(st["logits"], st["next"], st["keys"], T, k, p, ln, st["history"], st["step"])
+        else:
+            ops.argmax_advance(st["logits"], st["next"], ln, st["history"], st["step"])
 
     def _state(self, B: int, Lmax: int, f16: bool = False):
         c, dev = self.cfg, self.device
@@ -353,20 +392,30 @@ class MistralDecoder:
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int, attention_mask: torch.Tensor | None = None, past_key_values=None,
                  past_lens: torch.Tensor | None = None, eos_token_id: int | None = None, return_logits: bool = False,
-                 on_overflow: str | None = None, _force_bf16: bool = False):
-        """Greedy continuation.  ``input_ids`` [B,P]: the NEW prompt tokens (right-padded rows need ``attention_mask``; with
-        ``past_key_values`` all rows must be full length under ``prefill="rows"``, right-padded under ``"gemm"``).
+                 on_overflow: str | None = None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
+                 seed: int | None = None, num_return_sequences: int = 1, _force_bf16: bool = False):
+        """Greedy (or, with ``do_sample``, sampled) continuation.  ``input_ids`` [B,P]: the NEW prompt tokens (right-padded rows need
+        ``attention_mask``; with ``past_key_values`` all rows must be full length under ``prefill="rows"``, right-padded under ``"gemm"``).
         ``past_key_values``: per-layer K/V [B,nkv,S,d] of an already encoded prefix, e.g. the bidirectional document pass of ``encode(get_cache=True)``; ``past_lens`` [B] = valid prefix tokens per row
         (default S).  Returns the generated ids [B, max_new_tokens] (int64; positions after ``eos_token_id`` keep that id) and, with
         ``return_logits``, the logits of every generated position [B, max_new_tokens, V] (bf16; fp32 on fp16 operands).
 
         On fp16 operands (module docstring) a value beyond the fp16 range invalidates the call: ``on_overflow="raise"`` raises
         ``GritHipError``, ``"bf16"`` repeats the whole call in the bf16 arithmetic; default ``self.on_overflow`` ("raise";
-        ``GritLM(precision="auto").native_decoder()`` sets "bf16": the ladder's last rung)."""
+        ``GritLM(precision="auto").native_decoder()`` sets "bf16": the ladder's last rung).
+
+        ``do_sample``: each token is drawn as Hugging Face's multinomial sampling draws it -- ``temperature``, then ``top_k`` (0: off), then
+        ``top_p`` (1: off); defaults are GenerationConfig's -- by grit_sample_advance (semantics and RNG contract in include/gritlm_hip.h).
+        Row r of the call draws with key ``seed + r`` (mod 2^64); ``seed=None`` takes one from torch's default CPU generator.
+        ``num_return_sequences`` = n repeats every input row n times first (rows of one prompt consecutive, as ``repeat_interleave``), so
+        the call decodes B n rows and returns [B n, max_new_tokens].  The bf16 repeat of an fp16 overflow reuses the call's seed."""
         dev, c = self.device, self.cfg
         if self.prefill not in PREFILL_MODES:
             raise ValueError(f"MistralDecoder.prefill={self.prefill!r}: one of {PREFILL_MODES}")
-        B = input_ids.shape[0]
+        check_sampling(temperature, top_k, top_p, num_return_sequences, do_sample)
+        n = int(num_return_sequences)
+        attention_mask0, past_key_values0, past_lens0 = attention_mask, past_key_values, past_lens      # (the bf16 repeat expands again)
+        B = input_ids.shape[0] * n
         if B > MAX_ROWS:
             raise NotImplementedError(f"native decode: batch <= {MAX_ROWS} (got {B}); split the batch")
         if self.moe and B > GEMV_ROWS:
@@ -375,10 +424,18 @@ class MistralDecoder:
         on_overflow = self.on_overflow if on_overflow is None else on_overflow
         if on_overflow not in ("raise", "bf16"):
             raise ValueError(f"on_overflow={on_overflow!r}: 'raise' or 'bf16'")
+        if do_sample and seed is None:
+            seed = draw_seed()
         if f16:
             ops.f16_overflow_flag(dev, clear=True)        # a stale flag of an earlier call is not this call's
             self.eng._f16_weights(self.eng.layers[0])     # (refuses weights beyond the fp16 range before anything runs)
         ids = input_ids.to(device=dev, dtype=I64)
+        if n > 1:                                         # Hugging Face's expansion: the n copies of a row are consecutive
+            ids = ids.repeat_interleave(n, dim=0)
+            attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(n, dim=0)
+            past_lens = None if past_lens is None else past_lens.repeat_interleave(n, dim=0)
+            if past_key_values is not None:
+                past_key_values = [(k.repeat_interleave(n, dim=0), v.repeat_interleave(n, dim=0)) for k, v in _layers_of(past_key_values)]
         B, P = ids.shape
         nq, nkv, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         past = _layers_of(past_key_values) if past_key_values is not None else None
@@ -391,6 +448,8 @@ class MistralDecoder:
         Lmax = (S0 + P + max_new_tokens + 255) // 256 * 256
         st = self._state(B, Lmax, f16)
         st["history"] = torch.zeros((B, max_new_tokens), dtype=I64, device=dev)
+        if do_sample:
+            st["sampling"], st["keys"] = (float(temperature), int(top_k), float(top_p)), row_keys(seed, B, dev)
         logits_all = torch.empty((B, max_new_tokens, self.lm_head.shape[0]), dtype=st["logits"].dtype, device=dev) if return_logits else None
         if past is None:
             # prefill: one causal pass over the prompt that also emits the post-RoPE K/V (the encoder engine's forward)
@@ -451,7 +510,7 @@ class MistralDecoder:
         # first generated token from the prefill logits, then decode steps (graph replay)
         if return_logits:
             logits_all[:, 0].copy_(st["logits"])
-        ops.argmax_advance(st["logits"], st["next"], None, st["history"], st["step"])
+        self._sample(st, lens=False)
         graph = None
         for t in range(1, max_new_tokens):
             # Hugging Face's generate() stops once every row has emitted EOS; here the host only replays a graph, so it looks every 16
@@ -473,8 +532,9 @@ class MistralDecoder:
         self.last_precision = "f16" if f16 else ("bf16 (f16 overflow)" if _force_bf16 else "bf16")
         if f16 and (ops.f16_overflow_flag(dev, clear=True) or bool(st.get("cache_bad", False))):
             if on_overflow == "bf16":
-                return self.generate(input_ids, max_new_tokens, attention_mask=attention_mask, past_key_values=past_key_values, past_lens=past_lens,
-                                     eos_token_id=eos_token_id, return_logits=return_logits, _force_bf16=True)
+                return self.generate(input_ids, max_new_tokens, attention_mask=attention_mask0, past_key_values=past_key_values0,
+                                     past_lens=past_lens0, eos_token_id=eos_token_id, return_logits=return_logits, do_sample=do_sample,
+                                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, num_return_sequences=n, _force_bf16=True)
             raise GritHipError("native decode on fp16 operands: a value exceeded the fp16 range (activation, K/V or a cached K/V that was "
                                "already inf); the tokens of this call are invalid -- decode with precision 'bf16' (MistralDecoder.precision, "
                                "or on_overflow='bf16')")

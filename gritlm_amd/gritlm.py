@@ -299,14 +299,35 @@ class GritLM(torch.nn.Module):
         continuation of ``input_ids`` [B, P] (on top of the cached K/V when ``past_key_values`` is given -- then ``attention_mask`` is the
         reference's [B, cache + P] mask, ones over the cache), returned like Hugging Face's ``generate``: the input ids followed by the new
         tokens, positions after a sequence's EOS filled with ``pad_token_id``.  ``min_new_tokens`` is honoured when it equals
-        ``max_new_tokens`` (the reference's latency runs: EOS never stops a row) or is 0; sampling, beams and other generation options are
-        not native -- ``GritLM.generate`` (the Hugging Face method) stays available for them.
+        ``max_new_tokens`` (the reference's latency runs: EOS never stops a row) or is 0; sampling is ``sample_native``, beams and other
+        generation options are not native -- ``GritLM.generate`` (the Hugging Face method) stays available for them.
 
         Long inputs on top of a cache (the reference's query caching, rag/eval.py:200-238: the passage plus the prompt behind the query's
         cached K/V): ``m.native_decoder().prefill = "gemm"`` (or GRIT_DECODE_PREFILL=gemm) runs them through the encoder's MFMA GEMMs
         instead of the decode kernels, and accepts batched, right-padded inputs (the tail of ``attention_mask``)."""
         if do_sample or unsupported:
-            raise NotImplementedError(f"generate_native: greedy decoding only (got do_sample={do_sample}, {sorted(unsupported)}); use GritLM.generate")
+            raise NotImplementedError(f"generate_native: greedy decoding only (got do_sample={do_sample}, {sorted(unsupported)}); sampled "
+                                      "decoding on the native decoder is GritLM.sample_native, other options GritLM.generate")
+        return self._native_call(input_ids, attention_mask, past_key_values, max_new_tokens, min_new_tokens, pad_token_id, eos_token_id)
+
+    @torch.no_grad()
+    def sample_native(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None, past_key_values=None, max_new_tokens: int = 16,
+                      min_new_tokens: int = 0, pad_token_id: int | None = None, eos_token_id: int | None = None, temperature: float = 1.0,
+                      top_k: int = 50, top_p: float = 1.0, num_return_sequences: int = 1, seed: int | None = None) -> torch.Tensor:
+        """``model.generate(..., do_sample=True, temperature=, top_k=, top_p=, num_return_sequences=)`` on the native decoder: the call of
+        ``generate_native`` with every token drawn on the device (MistralDecoder.generate(do_sample=True): Hugging Face's temperature ->
+        top-k -> top-p warpers, then a Gumbel-max draw on Philox noise keyed by ``seed`` + row).  Returns [B n, P + new] like Hugging Face's
+        ``generate``: every input row repeated n times (consecutively), then its new tokens, pad after a row's EOS, the common tail trimmed.
+        ``seed=None`` draws the seed from torch's default CPU generator, so ``torch.manual_seed`` / ``transformers.set_seed`` reproduce a
+        call; the tokens are not those of ``torch.multinomial`` (another RNG)."""
+        return self._native_call(input_ids, attention_mask, past_key_values, max_new_tokens, min_new_tokens, pad_token_id, eos_token_id,
+                                 dict(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                      num_return_sequences=num_return_sequences))
+
+    def _native_call(self, input_ids, attention_mask, past_key_values, max_new_tokens, min_new_tokens, pad_token_id, eos_token_id,
+                     sampling: dict | None = None) -> torch.Tensor:
+        """generate_native / sample_native: the decoder call and Hugging Face's return value (inputs, then the new tokens with pad after
+        each row's EOS and the common tail of padding trimmed)."""
         if min_new_tokens not in (0, max_new_tokens):
             raise NotImplementedError("generate_native: min_new_tokens must be 0 or equal to max_new_tokens")
         dec = self.native_decoder()
@@ -317,7 +338,7 @@ class GritLM(torch.nn.Module):
             if mask.shape[1] != P:                    # the reference's mask spans cache + inputs: its tail is the inputs' own mask
                 mask = mask[:, mask.shape[1] - P:]
         eos = None if min_new_tokens == max_new_tokens else (eos_token_id if eos_token_id is not None else getattr(self.tokenizer, "eos_token_id", None))
-        new = dec.generate(ids, int(max_new_tokens), attention_mask=mask, past_key_values=past_key_values, eos_token_id=eos)
+        new = dec.generate(ids, int(max_new_tokens), attention_mask=mask, past_key_values=past_key_values, eos_token_id=eos, **(sampling or {}))
         if eos is not None:
             pad = pad_token_id if pad_token_id is not None else eos
             after = ((new == eos).long().cumsum(dim=1) - (new == eos).long()) > 0          # strictly after the first EOS of the row
@@ -326,6 +347,8 @@ class GritLM(torch.nn.Module):
             if bool(done.all()):                      # Hugging Face stops when every row has finished: trim the common tail of padding
                 keep = int(((new == eos).long().cumsum(dim=1) > 0).long().argmax(dim=1).max()) + 1
                 new = new[:, :keep]
+        if new.shape[0] != B:                         # num_return_sequences: the input rows repeated as Hugging Face returns them
+            ids = ids.repeat_interleave(new.shape[0] // B, dim=0)
         return torch.cat([ids, new.to(ids.dtype)], dim=1)
 
     # ------------------------------------------------------------------ API

@@ -868,6 +868,23 @@ def argmax_advance(logits: torch.Tensor, next_ids: torch.Tensor, lens: torch.Ten
     return next_ids
 
 
+def sample_advance(logits: torch.Tensor, next_ids: torch.Tensor, keys: torch.Tensor, temperature: float, top_k: int, top_p: float,
+                   lens: torch.Tensor | None = None, history: torch.Tensor | None = None, step: torch.Tensor | None = None):
+    """argmax_advance with a sampled token (grit_sample_advance[_f32]: temperature, top-k, top-p, Gumbel-max on Philox noise; semantics
+    and RNG contract in include/gritlm_hip.h).  ``keys``: int64 [B] row keys on the device (the bits of the uint64 keys); bf16 or fp32 logits."""
+    B, V = logits.shape
+    f32 = logits.dtype == F32
+    fn = _lib.load().grit_sample_advance_f32 if f32 else _lib.load().grit_sample_advance
+    if keys.numel() != B or next_ids.numel() < B or (lens is not None and lens.numel() < B) or (history is not None and history.shape[0] < B):
+        raise ValueError(f"sample_advance: {B} rows need B keys, next ids, lens and history rows")
+    check(fn(_chk2d(logits, F32 if f32 else BF16, "logits"), logits.stride(0), V, _chk(next_ids, I64, "next"),
+             0 if lens is None else _chk(lens, I32, "lens"), 0 if history is None else _chk(history, I64, "history"),
+             0 if history is None else history.stride(0), 0 if step is None else _chk(step, I32, "step"), B, _stream(),
+             float(temperature), min(int(top_k), 2 ** 31 - 1), float(top_p), _chk(keys, I64, "keys")),      # (top_k >= V keeps every token)
+          "grit_sample_advance_f32" if f32 else "grit_sample_advance")
+    return next_ids
+
+
 def knn_topk(queries: torch.Tensor, embeddings: torch.Tensor, k: int, transposed: bool = False):
     """Brute-force inner-product search: (scores [Q,k] fp32 descending, indices [Q,k] int64).  ``embeddings`` is [N,H], or with
     ``transposed=True`` the reference index layout [H,N] (rag/index.py:141); any strides."""

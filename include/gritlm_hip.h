@@ -460,6 +460,32 @@ int grit_attn_decode_rope_f16(const void* qkv, const float* cos_tab, const float
 int grit_argmax_advance_f32(const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history,
                             int64_t hist_stride, int32_t* step, int B, void* stream);
 
+/* Sampled step (csrc/sample.hip): the draw of Hugging Face's multinomial sampling (generation/utils.py: _get_logits_processor, _sample;
+ * the reference's sampled evaluation, scripts/generative_eval.sh: --do_sample True --temperature 0.2 --n_samples 20) in one launch per
+ * row batch, with the effect of grit_argmax_advance: next[b], history[b, *step], lens[b] += 1, then *step += 1 (a second, one-thread
+ * launch).  Arguments and contract as grit_argmax_advance (any V >= 1, ld % 8 == 0, 16-byte aligned logits, columns V .. ld-1 never
+ * read), plus temperature T, top_k, top_p and keys: B uint64 row keys in device memory.  grit_sample_advance reads bf16 logits,
+ * grit_sample_advance_f32 fp32 ones.  T > 0 and finite, 0 <= top_p <= 1, top_k >= 0 and keys != NULL, else GRIT_E_BADARG before any launch.
+ * Per row, in fp32:
+ *   1. s_v = logit_v / T (an fp32 division).  NaN and -inf scores are excluded (never drawn); a +inf score (a +inf logit, or a quotient
+ *      above the range) reads as FLT_MAX.  A row with no finite score writes token 0.
+ *   2. top_k: when 0 < top_k < V, keep s_v >= the top_k-th largest score (ties with it are kept, as TopKLogitsWarper keeps them).
+ *   3. top_p: when top_p < 1, with masses m_v = floor(exp(s_v - max s) * 2^32) (exp in fp32; the maximum weighs 2^32) and Z the sum of
+ *      the masses top_k kept: keep v iff the mass of kept tokens with a strictly larger score is < top_p * Z (in fp64), or v is a
+ *      maximum -- so top_p = 0 keeps the tied maxima.  This is TopPLogitsWarper's set wherever that set is well defined (its torch.sort
+ *      is unstable, so a tie straddling the boundary has no defined set there), with masses quantised to 2^-32 of the maximum's.
+ *      Both thresholds are exact selects on integer counts and masses: the same bits on every run.
+ *   4. The draw (Gumbel-max): token = argmax over the kept v of fp32(s_v + g_v), lowest index on ties.  RNG contract, fixed so that
+ *      seeded runs reproduce across releases: Philox4x32-10 with the Random123 constants, key (lo, hi) = the row's 64-bit key, counter
+ *      (v >> 2, t, 0, 0) with t = *step at the draw (0 without step), output word v & 3 = x; u_v = ((x >> 8) + 1/2) 2^-24 in (0, 1);
+ *      g_v = -log(E), E = -log(u_v), both in fp32 (E as -log1p(-(1 - u_v)) for u_v >= 1/2, where 1 - u_v is exact).
+ *   A row's token depends only on its logits, its key and t: not on B, the other rows, graph against eager or the launch geometry. */
+int grit_sample_advance(const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history, int64_t hist_stride,
+                        int32_t* step, int B, void* stream, float temperature, int top_k, float top_p, const uint64_t* keys);
+int grit_sample_advance_f32(const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history,
+                            int64_t hist_stride, int32_t* step, int B, void* stream, float temperature, int top_k, float top_p,
+                            const uint64_t* keys);
+
 /* Batched decode (the native decoder at 9..64 rows; what model.generate does for a batch, rag/eval.py:296-302): out[b,:] = x[b,:] W^T for
  * B = 1..64 rows on the MFMA (csrc/decode_gemm.hip), every weight element read once per launch.  Same arguments, epilogues, formats and
  * rounding points as grit_gemv_bf16 / grit_gemv_f16 / grit_rmsnorm_gemv_{bf16,f16}_deferred (STORE, RESIDUAL -- in place with
