@@ -704,87 +704,80 @@ static int launch_gemv(const void* x, const void* W, void* out, const void* res,
   return GRIT_OK;
 }
 
-// the fp16-operand forms (formats in the kernel's header comment); ln_w: the deferred norm
-static int gemv_entry_f16(const char* name, const void* x, const void* W, void* out, const void* ln_w, float eps, int B, int N, int K, int64_t ldx,
-                          int64_t ldw, int64_t ldo, int epilogue, const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream) {
-  if (B == 0) return GRIT_OK;
-  GRIT_REQUIRE(x && W && out, GRIT_E_BADARG, "%s: null pointer", name);
-  GRIT_REQUIRE(B > 0 && B <= 8, GRIT_E_UNSUPPORTED, "%s: B=%d rows (1..8; larger batches use grit_gemm_f16_nt)", name, B);
-  GRIT_REQUIRE(N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldx >= K && ldw >= K, GRIT_E_BADARG, "%s: bad sizes", name);
-  GRIT_REQUIRE(aligned16(x) && aligned16(W) && (!ln_w || aligned16(ln_w)), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", name);
-  hipStream_t st = (hipStream_t)stream;
-  const bool pn = ln_w != nullptr;
+// a STORE / SWIGLU launch by the norm in front of it: pn 0 none, 1 the exact fused norm (bf16 operands only), 2 the deferred one
+template <int MODE, bool F16, class... Args>
+static int launch_gemv_norm(int pn, Args... args) {
+  if constexpr (!F16) {
+    if (pn == 1) return launch_gemv<MODE, 1>(args...);
+  }
+  return pn == 2 ? launch_gemv<MODE, 2, F16>(args...) : launch_gemv<MODE, 0, F16>(args...);
+}
+
+// the epilogue's own checks and its launch, behind the other checks of an entry point (F16: the fp16-operand forms, formats in the
+// kernel's header comment; widx ...: the expert stack of grit_gemv_*_expert)
+template <bool F16>
+static int gemv_epilogue(const char* name, int epilogue, int pn, const void* x, const void* W, void* out, const void* ln_w, float eps, int B, int N,
+                         int K, int64_t ldx, int64_t ldw, int64_t ldo, const void* residual, int64_t ldr, void* out16, int64_t ldo16,
+                         hipStream_t st, const int32_t* widx = nullptr, int64_t w_estride = 0, int w_nexp = 0) {
   switch (epilogue) {
     case GRIT_EPI_STORE: GRIT_REQUIRE(ldo >= N, GRIT_E_BADARG, "%s: ldo < N", name);
-      return pn ? launch_gemv<0, 2, true>(x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st)
-                : launch_gemv<0, 0, true>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st);
+      return launch_gemv_norm<0, F16>(pn, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, widx, w_estride, w_nexp);
     case GRIT_EPI_RESIDUAL: GRIT_REQUIRE(residual && ldo >= N && ldr >= N && !pn, GRIT_E_BADARG, "%s: RESIDUAL needs residual, ldo, ldr >= N (no pre-norm)", name);
       GRIT_REQUIRE(!out16 || ldo16 >= N, GRIT_E_BADARG, "%s: ldo16 < N", name);
-      return launch_gemv<1, 0, true>(x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, st, out16, ldo16);
+      // (rows per workgroup of these launches -- o_proj, down: N = 4096 -> 1024 workgroups of 4 rows, half a workgroup wave -- and the
+      //  number of K-loop pieces a lane keeps in flight were A/B'd on one box: 1 / 2 / 4 rows 2.914 / 2.902 / 2.903 ms per token; 2 / 4
+      //  pieces in flight 2.963 / 3.139 against 2.921 -- more requests in flight are SLOWER; profiles/r05_decode_{rows,unroll}_ab.log)
+      return launch_gemv<1, 0, F16>(x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, st, out16, ldo16);
     case GRIT_EPI_SWIGLU: GRIT_REQUIRE(N % 32 == 0 && ldo >= N / 2, GRIT_E_UNSUPPORTED, "%s: SWIGLU needs N %% 32 == 0, ldo >= N/2", name);
-      return pn ? launch_gemv<2, 2, true>(x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st)
-                : launch_gemv<2, 0, true>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st);
+      return launch_gemv_norm<2, F16>(pn, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, widx, w_estride, w_nexp);
     default: GRIT_REQUIRE(false, GRIT_E_BADARG, "%s: unknown epilogue %d", name, epilogue);
   }
   return GRIT_OK;
 }
 
+// ln_w: the norm in front (fp16 operands: the deferred form only)
+template <bool F16>
 static int gemv_entry(const char* name, const void* x, const void* W, void* out, const void* ln_w, float eps, int B, int N, int K, int64_t ldx,
-                      int64_t ldw, int64_t ldo, int epilogue, const void* residual, int64_t ldr, void* stream, bool deferred = false) {
+                      int64_t ldw, int64_t ldo, int epilogue, const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream,
+                      bool deferred = F16) {
   if (B == 0) return GRIT_OK;
   GRIT_REQUIRE(x && W && out, GRIT_E_BADARG, "%s: null pointer", name);
-  GRIT_REQUIRE(B > 0 && B <= 8, GRIT_E_UNSUPPORTED, "%s: B=%d rows (1..8; larger batches use grit_gemm_bf16_nt)", name, B);
+  GRIT_REQUIRE(B > 0 && B <= 8, GRIT_E_UNSUPPORTED, "%s: B=%d rows (1..8; larger batches use grit_gemm_%s_nt)", name, B, F16 ? "f16" : "bf16");
   GRIT_REQUIRE(N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldx >= K && ldw >= K, GRIT_E_BADARG, "%s: bad sizes", name);
   GRIT_REQUIRE(aligned16(x) && aligned16(W) && (!ln_w || aligned16(ln_w)), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", name);
-  hipStream_t st = (hipStream_t)stream;
-  const bool pn = ln_w != nullptr;
-  switch (epilogue) {
-    case GRIT_EPI_STORE: GRIT_REQUIRE(ldo >= N, GRIT_E_BADARG, "%s: ldo < N", name);
-      return pn ? (deferred ? launch_gemv<0, 2>(x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st)
-                            : launch_gemv<0, 1>(x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st))
-                : launch_gemv<0, 0>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st);
-    case GRIT_EPI_RESIDUAL: GRIT_REQUIRE(residual && ldo >= N && ldr >= N && !pn, GRIT_E_BADARG, "%s: RESIDUAL needs residual, ldo, ldr >= N (no pre-norm)", name);
-      // (rows per workgroup of these launches -- o_proj, down: N = 4096 -> 1024 workgroups of 4 rows, half a workgroup wave -- and the
-      //  number of K-loop pieces a lane keeps in flight were A/B'd on one box: 1 / 2 / 4 rows 2.914 / 2.902 / 2.903 ms per token; 2 / 4
-      //  pieces in flight 2.963 / 3.139 against 2.921 -- more requests in flight are SLOWER; profiles/r05_decode_{rows,unroll}_ab.log)
-      return launch_gemv<1, 0>(x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, st);
-    case GRIT_EPI_SWIGLU: GRIT_REQUIRE(N % 32 == 0 && ldo >= N / 2, GRIT_E_UNSUPPORTED, "%s: SWIGLU needs N %% 32 == 0, ldo >= N/2", name);
-      return pn ? (deferred ? launch_gemv<2, 2>(x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st)
-                            : launch_gemv<2, 1>(x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st))
-                : launch_gemv<2, 0>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st);
-    default: GRIT_REQUIRE(false, GRIT_E_BADARG, "%s: unknown epilogue %d", name, epilogue);
-  }
-  return GRIT_OK;
+  return gemv_epilogue<F16>(name, epilogue, !ln_w ? 0 : deferred ? 2 : 1, x, W, out, ln_w, eps, B, N, K, ldx, ldw, ldo, residual, ldr, out16, ldo16,
+                            (hipStream_t)stream);
 }
 
 extern "C" int grit_gemv_bf16(const void* x, const void* W, void* out, int B, int N, int K, int64_t ldx, int64_t ldw, int64_t ldo, int epilogue,
                               const void* residual, int64_t ldr, void* stream) {
-  return gemv_entry("grit_gemv_bf16", x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, stream);
+  return gemv_entry<false>("grit_gemv_bf16", x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, nullptr, 0, stream);
 }
 
 extern "C" int grit_rmsnorm_gemv_bf16(const void* x, const void* ln_weight, float eps, const void* W, void* out, int B, int N, int K, int64_t ldx,
                                       int64_t ldw, int64_t ldo, int epilogue, void* stream) {
   GRIT_REQUIRE(ln_weight, GRIT_E_BADARG, "grit_rmsnorm_gemv_bf16: null pointer");
-  return gemv_entry("grit_rmsnorm_gemv_bf16", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0, stream);
+  return gemv_entry<false>("grit_rmsnorm_gemv_bf16", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0, nullptr, 0, stream);
 }
 
 extern "C" int grit_gemv_f16(const void* x, const void* W, void* out, int B, int N, int K, int64_t ldx, int64_t ldw, int64_t ldo, int epilogue,
                              const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream) {
   GRIT_REQUIRE(!out16 || epilogue == GRIT_EPI_RESIDUAL, GRIT_E_BADARG, "grit_gemv_f16: out16 goes with the RESIDUAL epilogue");
-  return gemv_entry_f16("grit_gemv_f16", x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, out16, ldo16, stream);
+  return gemv_entry<true>("grit_gemv_f16", x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, out16, ldo16, stream);
 }
 
 extern "C" int grit_rmsnorm_gemv_f16_deferred(const void* x, const void* ln_weight, float eps, const void* W, void* out, int B, int N, int K,
                                               int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream) {
   GRIT_REQUIRE(ln_weight, GRIT_E_BADARG, "grit_rmsnorm_gemv_f16_deferred: null pointer");
   GRIT_REQUIRE(epilogue != GRIT_EPI_RESIDUAL, GRIT_E_BADARG, "grit_rmsnorm_gemv_f16_deferred: STORE or SWIGLU");
-  return gemv_entry_f16("grit_rmsnorm_gemv_f16_deferred", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0, nullptr, 0, stream);
+  return gemv_entry<true>("grit_rmsnorm_gemv_f16_deferred", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0, nullptr, 0, stream);
 }
 
 // Sparse-MoE decode (ABI 6): x [B,K] times ONE matrix of a stack W [E,N,K] -- matrix expert[0], an index in DEVICE memory (the router's
 // choice for the row; w_expert_stride = elements between consecutive matrices; the kernel clamps the index to [0, E)) -- with the STORE or
 // SWIGLU epilogue.  f16: the fp16-operand formats of grit_gemv_f16 (STORE writes fp32, SWIGLU fp16).
-static int gemv_expert_entry(const char* name, bool f16, const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride,
+template <bool F16>
+static int gemv_expert_entry(const char* name, const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride,
                              int E, int B, int N, int K, int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream) {
   if (B == 0) return GRIT_OK;
   GRIT_REQUIRE(x && W && out && expert, GRIT_E_BADARG, "%s: null pointer", name);
@@ -793,34 +786,27 @@ static int gemv_expert_entry(const char* name, bool f16, const void* x, const vo
                ldw <= w_expert_stride / N, GRIT_E_BADARG, "%s: bad sizes", name);       // (stride >= N * ldw, without the product: fuzzed ldw overflows it)
   GRIT_REQUIRE(E >= 1 && (E == 1 || w_expert_stride <= INT64_MAX / (E - 1)), GRIT_E_BADARG, "%s: bad expert count E=%d", name, E);  // (E-1) * stride fits
   GRIT_REQUIRE(aligned16(x) && aligned16(W), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", name);
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case GRIT_EPI_STORE: GRIT_REQUIRE(ldo >= N, GRIT_E_BADARG, "%s: ldo < N", name);
-      return f16 ? launch_gemv<0, 0, true>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, expert, w_expert_stride, E)
-                 : launch_gemv<0, 0>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, expert, w_expert_stride, E);
-    case GRIT_EPI_SWIGLU: GRIT_REQUIRE(N % 32 == 0 && ldo >= N / 2, GRIT_E_UNSUPPORTED, "%s: SWIGLU needs N %% 32 == 0, ldo >= N/2", name);
-      return f16 ? launch_gemv<2, 0, true>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, expert, w_expert_stride, E)
-                 : launch_gemv<2, 0>(x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, expert, w_expert_stride, E);
-    default: GRIT_REQUIRE(false, GRIT_E_BADARG, "%s: epilogue %d (STORE or SWIGLU)", name, epilogue);
-  }
-  return GRIT_OK;
+  GRIT_REQUIRE(epilogue == GRIT_EPI_STORE || epilogue == GRIT_EPI_SWIGLU, GRIT_E_BADARG, "%s: epilogue %d (STORE or SWIGLU)", name, epilogue);
+  return gemv_epilogue<F16>(name, epilogue, 0, x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, nullptr, 0, nullptr, 0, (hipStream_t)stream, expert,
+                            w_expert_stride, E);
 }
 
 extern "C" int grit_gemv_bf16_expert(const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride, int E, int B, int N,
                                      int K, int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream) {
-  return gemv_expert_entry("grit_gemv_bf16_expert", false, x, W, out, expert, w_expert_stride, E, B, N, K, ldx, ldw, ldo, epilogue, stream);
+  return gemv_expert_entry<false>("grit_gemv_bf16_expert", x, W, out, expert, w_expert_stride, E, B, N, K, ldx, ldw, ldo, epilogue, stream);
 }
 
 extern "C" int grit_gemv_f16_expert(const void* x, const void* W, void* out, const int32_t* expert, int64_t w_expert_stride, int E, int B, int N,
                                     int K, int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream) {
-  return gemv_expert_entry("grit_gemv_f16_expert", true, x, W, out, expert, w_expert_stride, E, B, N, K, ldx, ldw, ldo, epilogue, stream);
+  return gemv_expert_entry<true>("grit_gemv_f16_expert", x, W, out, expert, w_expert_stride, E, B, N, K, ldx, ldw, ldo, epilogue, stream);
 }
 
 // the DEFERRED form of the fused norm (PRENORM 2 above): one launch, no second pass over x; x_n is not rounded to bf16
 extern "C" int grit_rmsnorm_gemv_bf16_deferred(const void* x, const void* ln_weight, float eps, const void* W, void* out, int B, int N, int K,
                                                int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream) {
   GRIT_REQUIRE(ln_weight, GRIT_E_BADARG, "grit_rmsnorm_gemv_bf16_deferred: null pointer");
-  return gemv_entry("grit_rmsnorm_gemv_bf16_deferred", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0, stream, true);
+  return gemv_entry<false>("grit_rmsnorm_gemv_bf16_deferred", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0, nullptr, 0, stream,
+                           true);
 }
 
 template <bool F16>

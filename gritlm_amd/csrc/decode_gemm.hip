@@ -246,7 +246,14 @@ int dg_run(const char* name, const void* x, const void* W, void* out, const void
   return GRIT_OK;
 }
 
-int dg_entry(const char* name, bool f16, const void* x, const void* W, void* out, const void* ln_w, float eps, int B, int N, int K,
+// STORE / SWIGLU with (pn) or without the deferred norm in front
+template <int MODE, bool F16, class... Args>
+int dg_run_norm(bool pn, Args... args) {
+  return pn ? dg_run<MODE, true, F16>(args...) : dg_run<MODE, false, F16>(args...);
+}
+
+template <bool F16>
+int dg_entry(const char* name, const void* x, const void* W, void* out, const void* ln_w, float eps, int B, int N, int K,
              int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream) {
   GRIT_REQUIRE(x && W && out, GRIT_E_BADARG, "%s: null pointer", name);
   GRIT_REQUIRE(B >= 1 && B <= 64, GRIT_E_UNSUPPORTED, "%s: B=%d rows (1..64)", name, B);
@@ -259,21 +266,14 @@ int dg_entry(const char* name, bool f16, const void* x, const void* W, void* out
   switch (epilogue) {
     case GRIT_EPI_STORE:
       GRIT_REQUIRE(ldo >= N, GRIT_E_BADARG, "%s: ldo < N", name);
-      if (f16) return pn ? dg_run<0, true, true>(name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream)
-                         : dg_run<0, false, true>(name, x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
-      return pn ? dg_run<0, true, false>(name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream)
-                : dg_run<0, false, false>(name, x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
+      return dg_run_norm<0, F16>(pn, name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
     case GRIT_EPI_RESIDUAL:
       GRIT_REQUIRE(residual && ldo >= N && ldr >= N && !pn, GRIT_E_BADARG, "%s: RESIDUAL needs residual, ldo, ldr >= N (no pre-norm)", name);
       GRIT_REQUIRE(!out16 || ldo16 >= N, GRIT_E_BADARG, "%s: ldo16 < N", name);
-      if (f16) return dg_run<1, false, true>(name, x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, out16, ldo16, stream);
-      return dg_run<1, false, false>(name, x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, nullptr, 0, stream);
+      return dg_run<1, false, F16>(name, x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, out16, ldo16, stream);
     case GRIT_EPI_SWIGLU:
       GRIT_REQUIRE(N % 32 == 0 && ldo >= N / 2, GRIT_E_UNSUPPORTED, "%s: SWIGLU needs N %% 32 == 0, ldo >= N/2", name);
-      if (f16) return pn ? dg_run<2, true, true>(name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream)
-                         : dg_run<2, false, true>(name, x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
-      return pn ? dg_run<2, true, false>(name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream)
-                : dg_run<2, false, false>(name, x, W, out, nullptr, nullptr, 0.f, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
+      return dg_run_norm<2, F16>(pn, name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
     default: GRIT_REQUIRE(false, GRIT_E_BADARG, "%s: unknown epilogue %d", name, epilogue);
   }
   return GRIT_OK;
@@ -283,20 +283,20 @@ int dg_entry(const char* name, bool f16, const void* x, const void* W, void* out
 
 extern "C" int grit_decode_gemm_bf16(const void* x, const void* W, void* out, int B, int N, int K, int64_t ldx, int64_t ldw, int64_t ldo,
                                      int epilogue, const void* residual, int64_t ldr, void* stream) {
-  return dg_entry("grit_decode_gemm_bf16", false, x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, nullptr, 0, stream);
+  return dg_entry<false>("grit_decode_gemm_bf16", x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, nullptr, 0, stream);
 }
 
 extern "C" int grit_decode_gemm_f16(const void* x, const void* W, void* out, int B, int N, int K, int64_t ldx, int64_t ldw, int64_t ldo,
                                     int epilogue, const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream) {
   GRIT_REQUIRE(!out16 || epilogue == GRIT_EPI_RESIDUAL, GRIT_E_BADARG, "grit_decode_gemm_f16: out16 goes with the RESIDUAL epilogue");
-  return dg_entry("grit_decode_gemm_f16", true, x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, out16, ldo16, stream);
+  return dg_entry<true>("grit_decode_gemm_f16", x, W, out, nullptr, 0.f, B, N, K, ldx, ldw, ldo, epilogue, residual, ldr, out16, ldo16, stream);
 }
 
 extern "C" int grit_rmsnorm_decode_gemm_bf16_deferred(const void* x, const void* ln_weight, float eps, const void* W, void* out, int B, int N,
                                                       int K, int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream) {
   GRIT_REQUIRE(ln_weight, GRIT_E_BADARG, "grit_rmsnorm_decode_gemm_bf16_deferred: null pointer");
   GRIT_REQUIRE(epilogue != GRIT_EPI_RESIDUAL, GRIT_E_BADARG, "grit_rmsnorm_decode_gemm_bf16_deferred: STORE or SWIGLU");
-  return dg_entry("grit_rmsnorm_decode_gemm_bf16_deferred", false, x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0,
+  return dg_entry<false>("grit_rmsnorm_decode_gemm_bf16_deferred", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0,
                   nullptr, 0, stream);
 }
 
@@ -304,6 +304,6 @@ extern "C" int grit_rmsnorm_decode_gemm_f16_deferred(const void* x, const void* 
                                                      int K, int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, void* stream) {
   GRIT_REQUIRE(ln_weight, GRIT_E_BADARG, "grit_rmsnorm_decode_gemm_f16_deferred: null pointer");
   GRIT_REQUIRE(epilogue != GRIT_EPI_RESIDUAL, GRIT_E_BADARG, "grit_rmsnorm_decode_gemm_f16_deferred: STORE or SWIGLU");
-  return dg_entry("grit_rmsnorm_decode_gemm_f16_deferred", true, x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0,
+  return dg_entry<true>("grit_rmsnorm_decode_gemm_f16_deferred", x, W, out, ln_weight, eps, B, N, K, ldx, ldw, ldo, epilogue, nullptr, 0,
                   nullptr, 0, stream);
 }

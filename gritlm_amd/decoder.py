@@ -20,6 +20,8 @@ continuation of ``encode(get_cache=True)`` at the north-star's own level (fp16 K
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import math
 import numbers
 
@@ -67,16 +69,46 @@ def draw_seed() -> int:
     return (hi << 32) | lo
 
 
+# What a pass over the layers launches is a small table, resolved once per call by MistralDecoder._plan.
+# The three forms of a norm site (input_layernorm -> q|k|v; post_attention_layernorm -> gate|up; final norm -> lm_head), _norm_proj:
+DEFERRED = "deferred"           # the row scale multiplies the finished dot products: x_n is not rounded (one rounding fewer than the reference)
+EXACT = "exact fused"           # the reference's two roundings inside the GEMV; above 8 rows the norm's own launch in front of the MFMA GEMM
+OWN = "own launch"              # rmsnorm, then the plain projection
+# The forms of a bf16 dense step by fuse_norm (any other value: as "qkv"); fp16 operands and sparse-MoE steps: DEFERRED, DEFERRED always.
+NORM_FORMS = {                  # q|k|v site, MLP and final sites
+    "deferred":     (DEFERRED, DEFERRED),
+    "deferred_mlp": (EXACT,    DEFERRED),
+    "all":          (EXACT,    EXACT),        # 3+ rows: OWN, OWN (_plan)
+    "qkv":          (EXACT,    OWN),          # 3+ rows: OWN, OWN
+    "none":         (OWN,      OWN),
+}
+# attn: "rope" (grit_attn_decode_rope: RoPE + K/V append + attention in one launch, behind every fused q|k|v site), "append"
+# (grit_rope_kv_append + grit_attn_decode, behind a q|k|v norm with its own launch) or, for a prompt chunk, "rows" (grit_rope_kv_append_rows +
+# grit_attn_decode_rows over all rows).  groups: the row ranges (a, b) a projection runs over, [None] for the whole batch.
+Plan = collections.namedtuple("Plan", "qkv_norm mlp_norm attn groups")
+
+
 def _proj(x: torch.Tensor, w: torch.Tensor, **kw):
     """x @ w^T of a decode step (epilogues of ops.gemv): the GEMV at 1..8 rows, the MFMA decode GEMM at 9..64."""
     return (ops.gemv if x.shape[0] <= GEMV_ROWS else ops.decode_gemm)(x, w, **kw)
 
 
-def _norm_proj(x: torch.Tensor, ln_w: torch.Tensor, eps: float, w: torch.Tensor, out: torch.Tensor, epilogue: int = EPI_STORE):
-    """the deferred RMSNorm + projection of a decode step: rmsnorm_gemv(deferred) at 1..8 rows, rmsnorm_decode_gemm at 9..64"""
-    if x.shape[0] <= GEMV_ROWS:
-        return ops.rmsnorm_gemv(x, ln_w, eps, w, out=out, epilogue=epilogue, deferred=True)
+def _norm_proj(form: str, x: torch.Tensor, ln_w: torch.Tensor, eps: float, w: torch.Tensor, out: torch.Tensor, xn: torch.Tensor | None,
+               epilogue: int = EPI_STORE):
+    """One norm site: RMSNorm + projection in the given form, at 1..8 rows on the GEMVs and at 9..64 on the MFMA decode GEMMs (``xn``: where
+    a norm with its own launch writes its rows)."""
+    gemv = x.shape[0] <= GEMV_ROWS
+    if form == OWN or (form == EXACT and not gemv):
+        ops.rmsnorm(x, ln_w, eps, out=xn)
+        return _proj(xn, w, out=out, epilogue=epilogue)
+    if gemv:
+        return ops.rmsnorm_gemv(x, ln_w, eps, w, out=out, epilogue=epilogue, deferred=form == DEFERRED)
     return ops.rmsnorm_decode_gemm(x, ln_w, eps, w, out=out, epilogue=epilogue)
+
+
+def _cut(t, g):
+    """rows g = (a, b) of a buffer; the whole of it for g = None (a step), None for no buffer"""
+    return t if g is None or t is None else t[g[0]:g[1]]
 
 
 def prefill_layout(attention_mask: torch.Tensor, lens: torch.Tensor, Lmax: int | None = None):
@@ -111,7 +143,7 @@ def _layers_of(cache):
 class MistralDecoder:
     def __init__(self, engine: MistralEncoderEngine, lm_head: torch.Tensor):
         self.eng, self.cfg, self.device = engine, engine.cfg, engine.device
-        self.moe = bool(engine.cfg.num_local_experts)      # sparse-MoE (Mixtral) layers: router + the two chosen experts per row (_step_moe)
+        self.moe = bool(engine.cfg.num_local_experts)      # sparse-MoE (Mixtral) layers: router + the two chosen experts per row (_layers_moe)
         self.lm_head = lm_head.detach().to(device=self.device, dtype=BF16).contiguous()
         self.use_graph = True
         # which RMSNorms ride inside the following GEMV (grit_rmsnorm_gemv_bf16): "all" (input_layernorm -> q|k|v, post_attention_layernorm
@@ -161,56 +193,88 @@ class MistralDecoder:
             self._lm_head16 = (key, w)
         return self._lm_head16[1]
 
-    def _step_f16(self, st):
-        """One decode step on fp16 operands: fp32 stream / q|k|v row / logits; fp16 weights, K/V and GEMV operand rows (h16 = the stream's
-        rounding, written by the residual epilogues; ctx; act); every norm in the deferred form (the row scale multiplies fp32 dot products)."""
-        c, e = self.cfg, self.eng
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        h, h16, qkv, ctx, act = st["h"], st["h16"], st["qkv"], st["ctx"], st["act"]
-        ops.embed_gather(e.embed, st["next"], out=h)
-        h16.copy_(h)                                   # (bf16 embedding rows: exact in fp16 inside its range)
-        for li, L in enumerate(e.layers):
-            wqkv, wo, wgu, wdown = e._f16_weights(L)
-            ck, cv = st["cache"][li]
-            _norm_proj(h16, L.ln1, eps, wqkv, qkv)
-            ops.attn_decode_rope(qkv, st["cos"], st["sin"], ck, cv, st["lens"], ctx, st["ws"], nq, nkv, d)
-            _proj(ctx, wo, out=h, epilogue=EPI_RESIDUAL, residual=h, out16=h16)
-            _norm_proj(h16, L.ln2, eps, wgu, act, epilogue=EPI_SWIGLU)
-            _proj(act, wdown, out=h, epilogue=EPI_RESIDUAL, residual=h, out16=h16)
-        _norm_proj(h16, e.norm, eps, self._lm_head_f16(), st["logits"])
+    def _plan(self, rows: int, f16: bool, chunk: bool = False) -> Plan:
+        """The launches of a pass over ``rows`` rows (a step's batch, or all B P rows of a prompt chunk), resolved once per call."""
+        if chunk:
+            # the projections in groups of 8 rows, so a chunk stays on the GEMV at any row count: its bits are the token-by-token path's at
+            # 1..8 sequences (generate() takes it for the DEFERRED, DEFERRED plans only)
+            return Plan(DEFERRED, DEFERRED, "rows", [(a, min(a + GEMV_ROWS, rows)) for a in range(0, rows, GEMV_ROWS)])
+        qkv_norm, mlp_norm = (DEFERRED, DEFERRED) if f16 or self.moe else NORM_FORMS.get(self.fuse_norm, NORM_FORMS["qkv"])
+        # beyond 2 rows the EXACT fused forms give the norm its own launch (they re-derive every row's RMS in every workgroup; same bits
+        # either way).  The DEFERRED forms keep their arithmetic at every batch size (round 6, ADVICE r05): x_n is not rounded to bf16 there,
+        # so switching to the un-fused norm at 3+ rows would make a row's logits -- and near-tie argmaxes -- depend on how many rows share
+        # the step; the price is the deferred form's per-row work in the GEMV at 3..8 rows (batch 4: 4.93 against 4.69 ms per step, one box).
+        # ("deferred_mlp" keeps its exact q|k|v norm fused at 3..8 rows as well.)
+        if rows > 2 and DEFERRED not in (qkv_norm, mlp_norm):
+            qkv_norm, mlp_norm = OWN, OWN
+        return Plan(qkv_norm, mlp_norm, "append" if qkv_norm == OWN else "rope", [None])
 
-    def _step_moe(self, st):
-        """One decode step of a sparse-MoE (Mixtral) model, MixtralSparseMoeBlock.forward (scripts/modeling_mixtral_gritlm.py:839-882) at 1..8
+    def _weights(self, L, f16: bool):
+        """(q|k|v, o, gate|up, down) of a layer in the operand format; a sparse-MoE layer: (q|k|v, o, w13 stack, w2 stack)"""
+        if f16:
+            return self.eng._f16_weights(L)
+        return (L.wqkv, L.wo, L.w13, L.w2) if self.moe else (L.wqkv, L.wo, L.wgu, L.wdown)
+
+    def _embed(self, r, ids: torch.Tensor):
+        ops.embed_gather(self.eng.embed, ids, out=r["h"])
+        if r["f16"]:
+            r["h16"].copy_(r["h"])                     # (bf16 embedding rows: exact in fp16 inside its range)
+
+    def _attention(self, plan: Plan, r, li: int, L, wqkv, wo, out16):
+        """The attention half of a layer, for every kind of pass: input_layernorm + q|k|v, RoPE + K/V append + attention, o_proj + residual.
+        ``r``: the rows' buffers (a step: the state itself); ``out16``: where the residual epilogue writes the stream's fp16 rounding."""
+        c = self.cfg
+        nq, nkv, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        h, qkv, ctx, cos, sin, lens, ws = r["h"], r["qkv"], r["ctx"], r["cos"], r["sin"], r["lens"], r["ws"]
+        ck, cv = r["cache"][li]
+        for g in plan.groups:
+            _norm_proj(plan.qkv_norm, _cut(r["xin"], g), L.ln1, c.rms_norm_eps, wqkv, _cut(qkv, g), r["x"])
+        if plan.attn == "rope":
+            ops.attn_decode_rope(qkv, cos, sin, ck, cv, lens, ctx, ws, nq, nkv, d)
+        elif plan.attn == "append":
+            ops.rope_kv_append(qkv, cos, sin, ck, cv, lens, nq, nkv, d)
+            ops.attn_decode(qkv, ck, cv, lens, ctx, ws, nq, nkv, d)
+        else:                                          # "rows": row v is the token at position lens[v] of sequence rows[v]
+            ops.rope_kv_append_rows(qkv, cos, sin, ck, cv, lens, r["rows"], nq, nkv, d)
+            ops.attn_decode_rows(qkv, ck, cv, lens, r["rows"], ctx, ws, nq, nkv, d)
+        for g in plan.groups:
+            hg = _cut(h, g)
+            _proj(_cut(ctx, g), wo, out=hg, epilogue=EPI_RESIDUAL, residual=hg, out16=_cut(out16, g))
+
+    def _layers(self, plan: Plan, r):
+        """Every dense layer over the rows of ``r`` (all sizes static, lengths on the device).  bf16: the stream h is its own operand; fp16
+        operands: fp32 stream / q|k|v row / logits, fp16 weights, K/V and operand rows (xin = h16 = the stream's rounding, written by the
+        residual epilogues; ctx; act).  The four projections of a layer run site by site, each over all row groups."""
+        eps = self.cfg.rms_norm_eps
+        for li, L in enumerate(self.eng.layers):
+            wqkv, wo, wgu, wdown = self._weights(L, r["f16"])
+            self._attention(plan, r, li, L, wqkv, wo, r["h16"])
+            for g in plan.groups:                      # post_attention_layernorm + gate|up + SwiGLU
+                _norm_proj(plan.mlp_norm, _cut(r["xin"], g), L.ln2, eps, wgu, _cut(r["act"], g), r["x"], epilogue=EPI_SWIGLU)
+            for g in plan.groups:
+                hg = _cut(r["h"], g)
+                _proj(_cut(r["act"], g), wdown, out=hg, epilogue=EPI_RESIDUAL, residual=hg, out16=_cut(r["h16"], g))
+
+    def _layers_moe(self, plan: Plan, st):
+        """The layers of a sparse-MoE (Mixtral) model, MixtralSparseMoeBlock.forward (scripts/modeling_mixtral_gritlm.py:839-882) at 1..8
         rows: the attention half as in the dense step; then the router's top-2 decision ON THE DEVICE (experts [B,2], weights [B,2]) and,
         per row and choice, the two GEMVs of the chosen expert -- ``grit_gemv_*_expert`` reads the expert index from device memory, so the
         step is still one HIP graph and streams 2 of the 8 experts' weights per row -- and the weighted combine.
         bf16: the reference's arithmetic (exact RMSNorm for the block input, router on those bf16 rows, ``grit_moe_combine`` rounding
         points).  fp16 operands: the router reads the fp32 stream (norm folded in, nothing rounded), the experts run on fp16 copies, the
         combine adds fp32 expert outputs into the fp32 stream."""
-        c, e = self.cfg, self.eng
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        f16 = st["f16"]
-        h, h16, qkv, ctx, x, act2, y2 = st["h"], st["h16"], st["qkv"], st["ctx"], st["x"], st["act2"], st["y2"]
-        experts, weights, rows_c = st["experts"], st["weights"], st["rows_c"]
-        B = h.shape[0]
-        ops.embed_gather(e.embed, st["next"], out=h)
-        if f16:
-            h16.copy_(h)
-        xin = h16 if f16 else h
-        for li, L in enumerate(e.layers):
-            wqkv, wo, w13, w2 = e._f16_weights(L) if f16 else (L.wqkv, L.wo, L.w13, L.w2)
-            ck, cv = st["cache"][li]
-            ops.rmsnorm_gemv(xin, L.ln1, eps, wqkv, out=qkv, deferred=True)
-            ops.attn_decode_rope(qkv, st["cos"], st["sin"], ck, cv, st["lens"], ctx, st["ws"], nq, nkv, d)
+        eps, f16 = self.cfg.rms_norm_eps, st["f16"]
+        h, h16, x, act2, y2 = st["h"], st["h16"], st["x"], st["act2"], st["y2"]
+        experts, weights = st["experts"], st["weights"]
+        for li, L in enumerate(self.eng.layers):
+            wqkv, wo, w13, w2 = self._weights(L, f16)
+            self._attention(plan, st, li, L, wqkv, wo, None)       # (no out16: the combine below rewrites h16)
             if f16:
-                ops.gemv(ctx, wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
                 ops.moe_router_top2(h, L.wgate, experts, weights, ln_w=L.ln2, eps=eps)
-            else:
-                ops.gemv(ctx, wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
             ops.rmsnorm(h, L.ln2, eps, out=x)              # (bf16 rows: the reference's x_n; fp16 rows under fp16 operands)
             if not f16:
                 ops.moe_router_top2(x, L.wgate, experts, weights)
-            for b in range(B):
+            for b in range(h.shape[0]):
                 for k in (0, 1):
                     r = 2 * b + k
                     ops.gemv_expert(x[b:b + 1], w13, experts[b, k:k + 1], out=act2[r:r + 1], epilogue=EPI_SWIGLU)
@@ -218,74 +282,26 @@ class MistralDecoder:
             if f16:
                 ops.moe_decode_combine_f32(h, h16, y2, weights)
             else:
-                ops.moe_combine(y2, rows_c, weights, h, out=h)
-        ops.rmsnorm_gemv(xin, e.norm, eps, self._lm_head_f16() if f16 else self.lm_head, out=st["logits"], deferred=True)
+                ops.moe_combine(y2, st["rows_c"], weights, h, out=h)
 
-    # ------------------------------------------------------------------ one decode step (all sizes static, lengths on the device)
-    def _step(self, st):
-        if self.moe:
-            return self._step_moe(st)
+    def _logits(self, form: str, st, x: torch.Tensor):
+        """final norm + lm_head of the rows ``x`` into st["logits"]"""
+        _norm_proj(form, x, self.eng.norm, self.cfg.rms_norm_eps, self._lm_head_f16() if st["f16"] else self.lm_head, st["logits"], st["x"])
+
+    def _logits_after_engine(self, st, hidden: torch.Tensor):
+        """The first logits after a prompt pass of the encoder engine, from each row's last valid token.  bf16: ``hidden`` is the final-norm
+        output.  fp16 operands: the un-normalised stream, rounded to fp16, through the deferred final norm + lm_head launch of the steps."""
         if st["f16"]:
-            return self._step_f16(st)
-        c, e = self.cfg, self.eng
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        h, qkv, ctx, act = st["h"], st["qkv"], st["ctx"], st["act"]
-        ops.embed_gather(e.embed, st["next"], out=h)
-        # beyond 2 rows the EXACT fused forms give the norm its own launch (they re-derive every row's RMS in every workgroup; same bits
-        # either way).  The DEFERRED forms keep their arithmetic at every batch size (round 6): x_n is not rounded to bf16 there,
-        # so switching to the un-fused norm at 3+ rows would make a row's logits -- and near-tie argmaxes -- depend on how many rows share
-        # the step; the price is the deferred form's per-row work in the GEMV at 3..8 rows (batch 4: 4.93 against 4.69 ms per step, one box).
-        if self.fuse_norm == "none" or (h.shape[0] > 2 and not self.fuse_norm.startswith("deferred")):
-            return self._step_unfused_norm(st)
-        dm = self.fuse_norm in ("deferred", "deferred_mlp")           # MLP / final norm in the deferred form
-        dq = self.fuse_norm == "deferred"                              # q|k|v norm as well
-        fuse_mlp = dm or self.fuse_norm == "all"
-        big = h.shape[0] > GEMV_ROWS                                   # 9..64 rows: the MFMA decode GEMMs (deferred forms only)
-        for li, L in enumerate(e.layers):
-            ck, cv = st["cache"][li]
-            if big and not dq:                                         # ("deferred_mlp": the exact q|k|v norm gets its own launch)
-                ops.rmsnorm(h, L.ln1, eps, out=st["x"])
-                ops.decode_gemm(st["x"], L.wqkv, out=qkv)
-            elif big:
-                ops.rmsnorm_decode_gemm(h, L.ln1, eps, L.wqkv, out=qkv)
-            else:
-                ops.rmsnorm_gemv(h, L.ln1, eps, L.wqkv, out=qkv, deferred=dq)         # input_layernorm + q/k/v projections
-            ops.attn_decode_rope(qkv, st["cos"], st["sin"], ck, cv, st["lens"], ctx, st["ws"], nq, nkv, d)   # RoPE + KV append + attention
-            _proj(ctx, L.wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
-            if fuse_mlp and big:
-                ops.rmsnorm_decode_gemm(h, L.ln2, eps, L.wgu, out=act, epilogue=EPI_SWIGLU)
-            elif fuse_mlp:
-                ops.rmsnorm_gemv(h, L.ln2, eps, L.wgu, out=act, epilogue=EPI_SWIGLU, deferred=dm)   # post_attention_layernorm + gate/up + SwiGLU
-            else:
-                ops.rmsnorm(h, L.ln2, eps, out=st["x"])
-                ops.gemv(st["x"], L.wgu, out=act, epilogue=EPI_SWIGLU)
-            _proj(act, L.wdown, out=h, epilogue=EPI_RESIDUAL, residual=h)
-        if fuse_mlp and big:
-            ops.rmsnorm_decode_gemm(h, e.norm, eps, self.lm_head, out=st["logits"])
-        elif fuse_mlp:
-            ops.rmsnorm_gemv(h, e.norm, eps, self.lm_head, out=st["logits"], deferred=dm)       # final norm + lm_head
+            self._logits(DEFERRED, st, hidden.to(F16))
         else:
-            ops.rmsnorm(h, e.norm, eps, out=st["x"])
-            ops.gemv(st["x"], self.lm_head, out=st["logits"])
+            _proj(hidden, self.lm_head, out=st["logits"])
 
-    def _step_unfused_norm(self, st):
-        """More than 2 rows: every workgroup of the fused kernel would re-derive each row's RMS, so the norm gets its own launch (the exact
-        forms "qkv" / "all" / "none"; above 8 rows the projections are the MFMA decode GEMMs)."""
-        c, e = self.cfg, self.eng
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        h, x, qkv, ctx, act = st["h"], st["x"], st["qkv"], st["ctx"], st["act"]
-        for li, L in enumerate(e.layers):
-            ck, cv = st["cache"][li]
-            ops.rmsnorm(h, L.ln1, eps, out=x)
-            _proj(x, L.wqkv, out=qkv)
-            ops.rope_kv_append(qkv, st["cos"], st["sin"], ck, cv, st["lens"], nq, nkv, d)
-            ops.attn_decode(qkv, ck, cv, st["lens"], ctx, st["ws"], nq, nkv, d)
-            _proj(ctx, L.wo, out=h, epilogue=EPI_RESIDUAL, residual=h)
-            ops.rmsnorm(h, L.ln2, eps, out=x)
-            _proj(x, L.wgu, out=act, epilogue=EPI_SWIGLU)
-            _proj(act, L.wdown, out=h, epilogue=EPI_RESIDUAL, residual=h)
-        ops.rmsnorm(h, e.norm, eps, out=x)
-        _proj(x, self.lm_head, out=st["logits"])
+    # ------------------------------------------------------------------ one decode step
+    def _step(self, st):
+        plan = st["plan"]
+        self._embed(st, st["next"])
+        (self._layers_moe if self.moe else self._layers)(plan, st)
+        self._logits(plan.mlp_norm, st, st["xin"])
 
     # ------------------------------------------------------------------ a prompt chunk on top of the cache, all its tokens at once
     def _prompt_rows(self, st, ids: torch.Tensor):
@@ -294,70 +310,65 @@ class MistralDecoder:
         lens + i (grit_rope_kv_append_rows), then every row attending to keys 0 .. lens + i of its sequence (grit_attn_decode_rows) --
         so the arithmetic per row is the token-by-token path's, bit for bit (tests: native_generate_prompt_chunk).  Leaves the logits after
         the last prompt token in st["logits"] and advances lens by P.  Built for the default (deferred-norm) step and the fp16 one."""
-        c, e, dev = self.cfg, self.eng, self.device
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
+        c, dev = self.cfg, self.device
+        nq, nkv, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         f16 = st["f16"]
         B, P = ids.shape
         V = B * P
         op, wide = (F16, F32) if f16 else (BF16, BF16)
         mk = lambda n, dt: torch.empty((V, n), dtype=dt, device=dev)
-        h, qkv, ctx, act = mk(c.hidden_size, wide), mk((nq + 2 * nkv) * d, wide), mk(nq * d, op), mk(c.intermediate_size, op)
-        h16 = mk(c.hidden_size, F16) if f16 else None
-        lens_v = (st["lens"].view(B, 1) + torch.arange(P, dtype=I32, device=dev).view(1, P)).reshape(V).contiguous()
-        rows_v = torch.arange(B, dtype=I32, device=dev).repeat_interleave(P).contiguous()
-        Lmax = st["cache"][0][0].shape[2]
-        ws = ops.attn_decode_workspace(V, nq, nkv, Lmax, dev)
-        ops.embed_gather(e.embed, ids.reshape(-1).contiguous(), out=h)
-        if f16:
-            h16.copy_(h)
-        groups = [(a, min(a + 8, V)) for a in range(0, V, 8)]
-        x_in = h16 if f16 else h                       # what a norm + GEMV launch reads
-        for li, L in enumerate(e.layers):
-            wqkv, wo, wgu, wdown = e._f16_weights(L) if f16 else (L.wqkv, L.wo, L.wgu, L.wdown)
-            ck, cv = st["cache"][li]
-            for a, b in groups:
-                ops.rmsnorm_gemv(x_in[a:b], L.ln1, eps, wqkv, out=qkv[a:b], deferred=True)
-            ops.rope_kv_append_rows(qkv, st["cos"], st["sin"], ck, cv, lens_v, rows_v, nq, nkv, d)
-            ops.attn_decode_rows(qkv, ck, cv, lens_v, rows_v, ctx, ws, nq, nkv, d)
-            for a, b in groups:
-                if f16:
-                    ops.gemv(ctx[a:b], wo, out=h[a:b], epilogue=EPI_RESIDUAL, residual=h[a:b], out16=h16[a:b])
-                else:
-                    ops.gemv(ctx[a:b], wo, out=h[a:b], epilogue=EPI_RESIDUAL, residual=h[a:b])
-            for a, b in groups:
-                ops.rmsnorm_gemv(x_in[a:b], L.ln2, eps, wgu, out=act[a:b], epilogue=EPI_SWIGLU, deferred=True)
-            for a, b in groups:
-                if f16:
-                    ops.gemv(act[a:b], wdown, out=h[a:b], epilogue=EPI_RESIDUAL, residual=h[a:b], out16=h16[a:b])
-                else:
-                    ops.gemv(act[a:b], wdown, out=h[a:b], epilogue=EPI_RESIDUAL, residual=h[a:b])
-        last = x_in.view(B, P, -1)[:, P - 1].contiguous()                  # the stream of every sequence's last prompt token
-        _norm_proj(last, e.norm, eps, self._lm_head_f16() if f16 else self.lm_head, st["logits"])             # (B rows: 9..64 on the MFMA)
+        h, h16 = mk(c.hidden_size, wide), mk(c.hidden_size, F16) if f16 else None
+        r = dict(st, h=h, h16=h16, xin=h16 if f16 else h, x=None, qkv=mk((nq + 2 * nkv) * d, wide), ctx=mk(nq * d, op), act=mk(c.intermediate_size, op),
+                 lens=(st["lens"].view(B, 1) + torch.arange(P, dtype=I32, device=dev).view(1, P)).reshape(V).contiguous(),
+                 rows=torch.arange(B, dtype=I32, device=dev).repeat_interleave(P).contiguous(),
+                 ws=ops.attn_decode_workspace(V, nq, nkv, st["cache"][0][0].shape[2], dev))
+        plan = self._plan(V, f16, chunk=True)
+        self._embed(r, ids.reshape(-1).contiguous())
+        self._layers(plan, r)
+        last = r["xin"].view(B, P, -1)[:, P - 1].contiguous()              # the stream of every sequence's last prompt token
+        self._logits(plan.mlp_norm, st, last)                               # (B rows: 9..64 on the MFMA)
         st["lens"] += P
+
+    @contextlib.contextmanager
+    def _engine_pass(self, f16: bool, causal: bool | None = None):
+        """A pass of the encoder engine under the decoder's arithmetic: a decoder on "f16" over a bf16 engine (or the reverse) switches the
+        engine's policy -- and, with ``causal``, its attention -- for the pass and restores both."""
+        e = self.eng
+        was = e.causal, e.precision
+        if f16 != (e.precision in F16_POLICIES):
+            e.precision = "f16_operands" if f16 else "bf16"
+        if causal is not None:
+            e.causal = causal
+        try:
+            yield e
+        finally:
+            e.causal, e.precision = was
 
     def _prompt_gemm(self, st, ids: torch.Tensor, mask: torch.Tensor):
         """The prompt chunk through the encoder engine's GEMMs on top of the cache (MistralEncoderEngine.forward_on_cache; the engine's
         policy switched for the pass as in the past=None prefill), the first logits from each row's last valid token through the same
         launch the past=None prefill uses; advances lens by each row's valid length."""
-        c, e, dev = self.cfg, self.eng, self.device
-        f16 = st["f16"]
-        Lmax = st["cache"][0][0].shape[2]
-        plen, pos, last = prefill_layout(mask, st["lens"], Lmax)
-        plen, pos, last = plen.to(dev), pos.to(dev), last.to(dev)
-        pol = e.precision
-        if f16 and pol not in F16_POLICIES:
-            e.precision = "f16_operands"
-        elif not f16 and pol in F16_POLICIES:
-            e.precision = "bf16"
-        try:
+        dev, f16 = self.device, st["f16"]
+        plen, pos, last = (t.to(dev) for t in prefill_layout(mask, st["lens"], st["cache"][0][0].shape[2]))
+        with self._engine_pass(f16) as e:
             hl = e.forward_on_cache(ids, st["cache"], st["lens"], plen, pos, last, final_norm=not f16)
-        finally:
-            e.precision = pol
-        if f16:
-            _norm_proj(hl.to(F16), e.norm, c.rms_norm_eps, self._lm_head_f16(), st["logits"])
-        else:
-            _proj(hl, self.lm_head, out=st["logits"])
+        self._logits_after_engine(st, hl)
         st["lens"] += plen
+
+    def _load_past(self, st, past, past_lens):
+        """The cached prefix into the step's cache: K/V, every row's valid length, and -- K/V narrowed to fp16 on their way in (a bf16 /
+        fp32 cache: values beyond 65504 became inf) -- a flag for non-finite values: they would surface as nan logits without touching
+        the device's overflow flag (the fp32 outputs are not range-checked)."""
+        dev, B, S0 = self.device, st["lens"].shape[0], past[0][0].shape[2]
+        for (ck, cv), (k, v) in zip(st["cache"], past):
+            ck[:, :, :S0].copy_(k.to(dev)); cv[:, :, :S0].copy_(v.to(dev))
+        if st["f16"] and any(k.dtype != F16 or v.dtype != F16 for k, v in past):
+            bad = torch.zeros((), dtype=torch.bool, device=dev)
+            for ck, cv in st["cache"]:
+                bad |= ~torch.isfinite(ck[:, :, :S0]).all()
+                bad |= ~torch.isfinite(cv[:, :, :S0]).all()
+            st["cache_bad"] = bad
+        st["lens"].copy_(torch.full((B,), S0, dtype=I32, device=dev) if past_lens is None else past_lens.to(device=dev, dtype=I32))
 
     def _sample(self, st, lens: bool = True):
         """the token of the step: the device argmax, or with st["sampling"] = (T, top_k, top_p) the sampled draw on the rows' keys"""
@@ -381,7 +392,9 @@ class MistralDecoder:
             moe = dict(act2=torch.empty((2 * B, c.intermediate_size), dtype=op, device=dev), y2=torch.empty((2 * B, c.hidden_size), dtype=wide, device=dev),
                        experts=torch.zeros((B, 2), dtype=I32, device=dev), weights=torch.zeros((B, 2), dtype=F32, device=dev),
                        rows_c=torch.arange(2 * B, dtype=I32, device=dev).view(B, 2).contiguous())
-        return dict(**moe, f16=f16, h=mk(c.hidden_size, wide), h16=mk(c.hidden_size, F16) if f16 else None, x=mk(c.hidden_size, op), qkv=mk((nq + 2 * nkv) * d, wide), ctx=mk(nq * d, op),
+        h, h16 = mk(c.hidden_size, wide), mk(c.hidden_size, F16) if f16 else None
+        # (xin: what a norm + projection launch reads of the stream -- its fp16 rounding under fp16 operands)
+        return dict(**moe, f16=f16, plan=self._plan(B, f16), h=h, h16=h16, xin=h16 if f16 else h, x=mk(c.hidden_size, op), qkv=mk((nq + 2 * nkv) * d, wide), ctx=mk(nq * d, op),
                     act=mk(c.intermediate_size, op), logits=mk(self.lm_head.shape[0], wide), next=torch.zeros((B,), dtype=I64, device=dev),
                     lens=torch.zeros((B,), dtype=I32, device=dev), step=torch.zeros((1,), dtype=I32, device=dev), cos=cos, sin=sin,
                     ws=ops.attn_decode_workspace(B, nq, nkv, Lmax, dev),
@@ -458,44 +471,25 @@ class MistralDecoder:
             # fp16 K/V go into the cache as they are and the first token's logits come from the un-normalised stream of the last prompt
             # token through the same deferred norm + lm_head launch the decode steps use.  A decoder pinned to "f16" on a bf16 engine
             # (or the reverse) switches the engine's policy for the pass and restores it.
-            was, pol = self.eng.causal, self.eng.precision
-            if f16 and pol not in F16_POLICIES:
-                self.eng.precision = "f16_operands"
-            elif not f16 and pol in F16_POLICIES:
-                self.eng.precision = "bf16"
-            self.eng.causal = True
-            try:
-                hidden, kv = self.eng.forward(ids, mask, borrow=True, return_kv=True, final_norm=not f16, kv_dtype=None if f16 else BF16)
-            finally:
-                self.eng.causal, self.eng.precision = was, pol
+            with self._engine_pass(f16, causal=True) as e:
+                hidden, kv = e.forward(ids, mask, borrow=True, return_kv=True, final_norm=not f16, kv_dtype=None if f16 else BF16)
             for li, (k, v) in enumerate(kv):
                 st["cache"][li][0][:, :, :P].copy_(k); st["cache"][li][1][:, :, :P].copy_(v)
             plen = mask.sum(dim=1).to(I32)
             st["lens"].copy_(plen)
             self.last_prefill = "encoder"
             last = hidden[torch.arange(B, device=dev), (plen - 1).long()].contiguous()              # [B,H] of the last prompt token
-            if f16:
-                _norm_proj(last.to(F16), self.eng.norm, c.rms_norm_eps, self._lm_head_f16(), st["logits"])
-            else:
-                _proj(last, self.lm_head, out=st["logits"])                                          # (final-norm output, bf16)
+            self._logits_after_engine(st, last)
         elif self.prefill == "gemm" and P > 0:
             mask = torch.ones((B, P), dtype=I64, device=dev) if attention_mask is None else attention_mask.to(device=dev, dtype=I64)
             prefill_layout(mask, torch.zeros((B,), dtype=I32, device=dev))        # (refuses a mask that is not right-padded before anything runs)
-            for li, (k, v) in enumerate(past):
-                st["cache"][li][0][:, :, :S0].copy_(k.to(dev)); st["cache"][li][1][:, :, :S0].copy_(v.to(dev))
-            if f16 and any(k.dtype != F16 or v.dtype != F16 for k, v in past):
-                self._flag_nonfinite_cache(st, S0)
-            st["lens"].copy_(torch.full((B,), S0, dtype=I32, device=dev) if past_lens is None else past_lens.to(device=dev, dtype=I32))
+            self._load_past(st, past, past_lens)
             self._prompt_gemm(st, ids, mask)
             self.last_prefill = "gemm"
         else:
             if attention_mask is not None and not bool((attention_mask != 0).all()):
                 raise NotImplementedError("native decode: padded prompt rows on top of past_key_values")
-            for li, (k, v) in enumerate(past):
-                st["cache"][li][0][:, :, :S0].copy_(k.to(dev)); st["cache"][li][1][:, :, :S0].copy_(v.to(dev))
-            if f16 and any(k.dtype != F16 or v.dtype != F16 for k, v in past):
-                self._flag_nonfinite_cache(st, S0)        # (a bf16 / fp32 cache narrowed to fp16: values beyond 65504 became inf)
-            st["lens"].copy_(torch.full((B,), S0, dtype=I32, device=dev) if past_lens is None else past_lens.to(device=dev, dtype=I32))
+            self._load_past(st, past, past_lens)
             # the prompt rides on the decode path: all its tokens at once (_prompt_rows: the step's own kernels over B P rows), or, for the
             # exact-norm forms and very long prompts, one token per step (teacher forced); its K/V land behind the cached prefix
             if P > 0 and self.prompt_chunk and (f16 or self.fuse_norm == "deferred") and B * P <= self.prompt_chunk_max_rows:
@@ -521,7 +515,9 @@ class MistralDecoder:
                 graph.replay()
             else:
                 self._step(st)
-                self._sample_step(st, logits_all, t)
+                if logits_all is not None:
+                    logits_all[:, t].copy_(st["logits"])
+                self._sample(st)
                 if self.use_graph and logits_all is None and t + 1 < max_new_tokens:
                     torch.cuda.synchronize()
                     graph = torch.cuda.CUDAGraph()
@@ -542,17 +538,3 @@ class MistralDecoder:
             hit = (out == eos_token_id).long().cumsum(dim=1) > 0
             out = torch.where(hit, torch.full_like(out, eos_token_id), out)
         return (out, logits_all) if return_logits else out
-
-    def _flag_nonfinite_cache(self, st, n: int):
-        """K/V narrowed to fp16 on their way into the cache: a value beyond the range would surface as nan logits without touching the
-        device's overflow flag (the fp32 outputs are not range-checked) -- raise it here."""
-        bad = torch.zeros((), dtype=torch.bool, device=self.device)
-        for ck, cv in st["cache"]:
-            bad |= ~torch.isfinite(ck[:, :, :n]).all()
-            bad |= ~torch.isfinite(cv[:, :, :n]).all()
-        st["cache_bad"] = bad
-
-    def _sample_step(self, st, logits_all, t):
-        if logits_all is not None:
-            logits_all[:, t].copy_(st["logits"])
-        self._sample(st)

@@ -609,28 +609,35 @@ def attn_bidir_varlen_bwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_len: 
     return dqkv
 
 
+def _proj_args(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None, epilogue: int, ln_w: torch.Tensor | None = None, eps: float = 0.0):
+    """What the decode projections (gemv, decode_gemm and their rmsnorm forms) share: out [B, N] (N // 2 under SWIGLU) in the format the
+    weights and the epilogue give (bf16 weights: bf16; fp16 weights: fp32, under SWIGLU the fp16 activation), allocated when absent, and
+    the checked head of the C argument list: x, [ln_w, eps,] w, out, B, N, K, ldx, ldw, ldo, epilogue.  Returns (out, fp16 operands?, head)."""
+    B, K = x.shape
+    N = w.shape[0]
+    f16 = w.dtype == F16
+    op, odt = (F16, F16 if epilogue == EPI_SWIGLU else F32) if f16 else (BF16, BF16)
+    if out is None:
+        out = torch.empty((B, N // 2 if epilogue == EPI_SWIGLU else N), dtype=odt, device=x.device)
+    norm = [] if ln_w is None else [_chk(ln_w, BF16, "ln_w"), float(eps)]
+    return out, f16, [_chk2d(x, op, "x"), *norm, _chk2d(w, op, "w"), _chk2d(out, odt, "out"), B, N, K, x.stride(0), w.stride(0), out.stride(0), epilogue]
+
+
+def _ptr_ld(t: torch.Tensor | None, dtype, name: str):
+    """(pointer, row stride) of an optional 2-d argument; (0, 0) without it"""
+    return (0, 0) if t is None else (_chk2d(t, dtype, name), t.stride(0))
+
+
 def gemv(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None, epilogue: int = EPI_STORE,
          residual: torch.Tensor | None = None, out16: torch.Tensor | None = None) -> torch.Tensor:
     """out[B,N] = x[B,K] @ w[N,K]^T for B <= 8 rows (decode); same epilogues as gemm_nt.  fp16 ``w`` (and ``x``): the fp16-operand form --
     STORE / RESIDUAL write fp32 (``residual`` is the fp32 stream; ``out16``: additionally its fp16 rounding, the next GEMV's operand),
     SWIGLU writes the fp16 activation."""
-    B, K = x.shape
-    N = w.shape[0]
-    n_out = N // 2 if epilogue == EPI_SWIGLU else N
-    if w.dtype == F16:
-        odt = F16 if epilogue == EPI_SWIGLU else F32
-        if out is None:
-            out = torch.empty((B, n_out), dtype=odt, device=x.device)
-        check(_lib.load().grit_gemv_f16(_chk2d(x, F16, "x"), _chk2d(w, F16, "w"), _chk2d(out, odt, "out"), B, N, K, x.stride(0), w.stride(0),
-                                        out.stride(0), epilogue, 0 if residual is None else _chk2d(residual, F32, "residual"),
-                                        0 if residual is None else residual.stride(0), 0 if out16 is None else _chk2d(out16, F16, "out16"),
-                                        0 if out16 is None else out16.stride(0), _stream()), "grit_gemv_f16")
-        return out
-    if out is None:
-        out = torch.empty((B, n_out), dtype=BF16, device=x.device)
-    check(_lib.load().grit_gemv_bf16(_chk2d(x, BF16, "x"), _chk2d(w, BF16, "w"), _chk2d(out, BF16, "out"), B, N, K, x.stride(0), w.stride(0),
-                                     out.stride(0), epilogue, 0 if residual is None else _chk2d(residual, BF16, "residual"),
-                                     0 if residual is None else residual.stride(0), _stream()), "grit_gemv_bf16")
+    out, f16, args = _proj_args(x, w, out, epilogue)
+    if f16:
+        check(_lib.load().grit_gemv_f16(*args, *_ptr_ld(residual, F32, "residual"), *_ptr_ld(out16, F16, "out16"), _stream()), "grit_gemv_f16")
+    else:
+        check(_lib.load().grit_gemv_bf16(*args, *_ptr_ld(residual, BF16, "residual"), _stream()), "grit_gemv_bf16")
     return out
 
 
@@ -681,24 +688,14 @@ def rmsnorm_gemv(x: torch.Tensor, ln_w: torch.Tensor, eps: float, w: torch.Tenso
     """gemv(rmsnorm(x, ln_w, eps), w) in one launch (decode step).  ``deferred``: the row scale multiplies the finished dot products
     (no pass over x in front of the weight stream; x_n is not rounded to bf16: not the bits of the two launches).  fp16 ``w``: x is the
     fp16 copy of the residual stream, the deferred form only; STORE writes fp32, SWIGLU the fp16 activation."""
-    B, K = x.shape
-    N = w.shape[0]
-    n_out = N // 2 if epilogue == EPI_SWIGLU else N
-    if w.dtype == F16:
-        if not deferred:
-            raise ValueError("rmsnorm_gemv on fp16 weights: the deferred form only")
-        odt = F16 if epilogue == EPI_SWIGLU else F32
-        if out is None:
-            out = torch.empty((B, n_out), dtype=odt, device=x.device)
-        check(_lib.load().grit_rmsnorm_gemv_f16_deferred(_chk2d(x, F16, "x"), _chk(ln_w, BF16, "ln_w"), float(eps), _chk2d(w, F16, "w"),
-                                                         _chk2d(out, odt, "out"), B, N, K, x.stride(0), w.stride(0), out.stride(0), epilogue,
-                                                         _stream()), "grit_rmsnorm_gemv_f16_deferred")
-        return out
-    if out is None:
-        out = torch.empty((B, n_out), dtype=BF16, device=x.device)
-    fn = _lib.load().grit_rmsnorm_gemv_bf16_deferred if deferred else _lib.load().grit_rmsnorm_gemv_bf16
-    check(fn(_chk2d(x, BF16, "x"), _chk(ln_w, BF16, "ln_w"), float(eps), _chk2d(w, BF16, "w"), _chk2d(out, BF16, "out"),
-             B, N, K, x.stride(0), w.stride(0), out.stride(0), epilogue, _stream()), "grit_rmsnorm_gemv_bf16")
+    if w.dtype == F16 and not deferred:
+        raise ValueError("rmsnorm_gemv on fp16 weights: the deferred form only")
+    out, f16, args = _proj_args(x, w, out, epilogue, ln_w, eps)
+    if f16:
+        check(_lib.load().grit_rmsnorm_gemv_f16_deferred(*args, _stream()), "grit_rmsnorm_gemv_f16_deferred")
+    else:
+        fn = _lib.load().grit_rmsnorm_gemv_bf16_deferred if deferred else _lib.load().grit_rmsnorm_gemv_bf16
+        check(fn(*args, _stream()), "grit_rmsnorm_gemv_bf16")
     return out
 
 
@@ -707,23 +704,12 @@ def decode_gemm(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = Non
     """out[B,N] = x[B,K] @ w[N,K]^T for 1..64 rows on the MFMA (batched decode: the step's projections above 8 rows); the epilogues and
     formats of ``gemv`` (fp16 ``w``: STORE / RESIDUAL write fp32, ``out16`` the fp16 copy, SWIGLU the fp16 activation).  A row's output
     does not depend on B or on the other rows, bit for bit; it differs from ``gemv``'s in the last bits (another summation order)."""
-    B, K = x.shape
-    N = w.shape[0]
-    n_out = N // 2 if epilogue == EPI_SWIGLU else N
-    if w.dtype == F16:
-        odt = F16 if epilogue == EPI_SWIGLU else F32
-        if out is None:
-            out = torch.empty((B, n_out), dtype=odt, device=x.device)
-        check(_lib.load().grit_decode_gemm_f16(_chk2d(x, F16, "x"), _chk2d(w, F16, "w"), _chk2d(out, odt, "out"), B, N, K, x.stride(0),
-                                               w.stride(0), out.stride(0), epilogue, 0 if residual is None else _chk2d(residual, F32, "residual"),
-                                               0 if residual is None else residual.stride(0), 0 if out16 is None else _chk2d(out16, F16, "out16"),
-                                               0 if out16 is None else out16.stride(0), _stream()), "grit_decode_gemm_f16")
-        return out
-    if out is None:
-        out = torch.empty((B, n_out), dtype=BF16, device=x.device)
-    check(_lib.load().grit_decode_gemm_bf16(_chk2d(x, BF16, "x"), _chk2d(w, BF16, "w"), _chk2d(out, BF16, "out"), B, N, K, x.stride(0),
-                                            w.stride(0), out.stride(0), epilogue, 0 if residual is None else _chk2d(residual, BF16, "residual"),
-                                            0 if residual is None else residual.stride(0), _stream()), "grit_decode_gemm_bf16")
+    out, f16, args = _proj_args(x, w, out, epilogue)
+    if f16:
+        check(_lib.load().grit_decode_gemm_f16(*args, *_ptr_ld(residual, F32, "residual"), *_ptr_ld(out16, F16, "out16"), _stream()),
+              "grit_decode_gemm_f16")
+    else:
+        check(_lib.load().grit_decode_gemm_bf16(*args, *_ptr_ld(residual, BF16, "residual"), _stream()), "grit_decode_gemm_bf16")
     return out
 
 
@@ -731,16 +717,9 @@ def rmsnorm_decode_gemm(x: torch.Tensor, ln_w: torch.Tensor, eps: float, w: torc
                         epilogue: int = EPI_STORE) -> torch.Tensor:
     """decode_gemm with the DEFERRED RMSNorm of x folded in (the row scale multiplies the finished fp32 sums; x * ln_w is rounded once to
     the operand format for the MFMA).  1..64 rows; STORE or SWIGLU; fp16 ``w``: x is the fp16 copy of the stream, STORE writes fp32."""
-    B, K = x.shape
-    N = w.shape[0]
-    n_out = N // 2 if epilogue == EPI_SWIGLU else N
-    f16 = w.dtype == F16
-    odt = (F16 if epilogue == EPI_SWIGLU else F32) if f16 else BF16
-    if out is None:
-        out = torch.empty((B, n_out), dtype=odt, device=x.device)
+    out, f16, args = _proj_args(x, w, out, epilogue, ln_w, eps)
     fn = _lib.load().grit_rmsnorm_decode_gemm_f16_deferred if f16 else _lib.load().grit_rmsnorm_decode_gemm_bf16_deferred
-    check(fn(_chk2d(x, F16 if f16 else BF16, "x"), _chk(ln_w, BF16, "ln_w"), float(eps), _chk2d(w, F16 if f16 else BF16, "w"),
-             _chk2d(out, odt, "out"), B, N, K, x.stride(0), w.stride(0), out.stride(0), epilogue, _stream()), "grit_rmsnorm_decode_gemm")
+    check(fn(*args, _stream()), "grit_rmsnorm_decode_gemm")
     return out
 
 
