@@ -117,6 +117,160 @@ def rope_tables(seq_len: int, head_dim: int, theta: float, round_bf16: bool, dev
     return cos.contiguous().to(device), sin.contiguous().to(device)
 
 
+class Geometry:
+    """The rows of one call.  ``padded``: T = B*S rows, key-padding bitmask.  ``packed``: only the real tokens of a right-padded batch
+    (rows of sequence b at [cu[b], cu[b+1])), per-row RoPE positions -- GEMMs, norms and attention never see padding (the reference
+    computes every padded position).  ``cached``: a chunk of S prompt rows per sequence behind ``lens[b]`` cached keys,
+    ``plen[b]`` of them valid, row positions lens[b] + i.  ``causal`` / ``window``: the attention mode of the padded and packed forms."""
+    __slots__ = ("form", "B", "S", "T", "bits", "cu", "pos", "max_len", "keep", "causal", "window", "lens", "plen")
+
+    def __init__(self, form: str, B: int, S: int, T: int, **kw):
+        self.form, self.B, self.S, self.T, self.max_len, self.causal, self.window = form, B, S, T, S, False, 0
+        self.bits = self.cu = self.pos = self.keep = self.lens = self.plen = None
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    @property
+    def packed(self) -> bool:
+        return self.form == "packed"
+
+    @classmethod
+    def padded(cls, mask: torch.Tensor, causal: bool = False, window: int = 0):
+        B, S = mask.shape
+        return cls("padded", B, S, B * S, bits=ops.mask_pack(mask), causal=causal, window=window)
+
+    @classmethod
+    def from_mask(cls, mask: torch.Tensor, packed: bool | None = None, device=None, causal: bool = False, window: int = 0):
+        """Packed geometry on ``device`` (default: the mask's) -- ``packed=None``: when the mask is right-padded with no empty row, else
+        None.  A HOST mask is laid out on the host: no device synchronisation, and only real tokens cross PCIe (``keep`` selects them).
+        On a device mask one transfer decides the layout; the boolean-mask gather of the positions synchronises as well (and so does
+        every gather by ``keep`` the caller makes)."""
+        B, S = mask.shape
+        keep = mask != 0
+        lens = keep.sum(dim=1)
+        ar = torch.arange(S, device=mask.device)
+        # (right-padded?, no empty rows?), longest row, number of tokens: one transfer decides the layout
+        ok, max_len, T = torch.stack([(((ar.unsqueeze(0) < lens.unsqueeze(1)) == keep).all() & (lens > 0).all()).to(torch.int64),
+                                      lens.max(), lens.sum()]).tolist()
+        if not (ok if packed is None else packed):
+            return None
+        dev = mask.device if device is None else device
+        cu = torch.zeros((B + 1,), dtype=torch.int32, device=mask.device)
+        cu[1:] = torch.cumsum(lens, dim=0)
+        pos = ar.to(torch.int32).unsqueeze(0).expand(B, S)[keep].contiguous()              # row-major order == sequence order
+        return cls("packed", B, S, int(T), max_len=int(max_len), keep=keep, cu=cu.to(dev, non_blocking=True), pos=pos.to(dev, non_blocking=True),
+                   causal=causal, window=window)
+
+
+def epi_residual(h: torch.Tensor) -> int:
+    """the residual epilogue of a GEMM that adds into the stream ``h``"""
+    return EPI_RESIDUAL_F32 if h.dtype == torch.float32 else EPI_RESIDUAL
+
+
+def keyed(hit, key, make):
+    """(key, value): ``hit`` while its key still matches, else a fresh pair.  The rule of the fp16 weight copies and the fp16 embedding
+    table, keyed on their sources' storage and version counters: weights reloaded or updated in place are converted again."""
+    return hit if hit is not None and hit[0] == key else (key, make())
+
+
+def embed_table_f16(hit, embed: torch.Tensor):
+    """(key, fp16 copy of embed_tokens) for the fp16 residual stream (262 MB at V 32000): ``hit`` while the table is unchanged, else
+    converted again; a table beyond the fp16 range is refused.  The owner keeps the pair and hands it back in."""
+    e = embed.detach()
+
+    def convert():
+        if bool((e.abs() >= 65520.0).any()):
+            raise GritHipError("precision='f16_stream': embedding weights exceed the fp16 range")
+        return e.to(F16)
+    return keyed(hit, (e.data_ptr(), embed._version, tuple(e.shape)), convert)
+
+
+def cached_rope_tables(store: dict, c: EncoderConfig, S: int, rounded: bool, device):
+    t = store.get((S, rounded))
+    if t is None:
+        t = store[(S, rounded)] = rope_tables(S, c.head_dim, c.rope_theta, rounded, device)
+    return t
+
+
+def workspace(store: dict, c: EncoderConfig, device, T: int, precision: str, out_rows: bool) -> dict:
+    """Activation buffers of a no-grad forward over T token rows under ``precision``, kept in ``store``: one allocation sized for the
+    largest T seen, handed out as row-slices (ragged / packed batches change T every call).  ``out_rows``: with ``xo``, rows for a bf16
+    last_hidden_state that lives in the workspace (a forward whose result is a fresh tensor does not need them)."""
+    if store.get("cap", 0) < T or store.get("policy") != precision:       # (another policy: the stream / the operands have another dtype)
+        qkv_w = (c.num_attention_heads + 2 * c.num_key_value_heads) * c.head_dim
+        store.clear()
+        opd = F16 if precision in F16_POLICIES else BF16
+        mk = lambda n: torch.empty((T, n), dtype=opd, device=device)
+        h = torch.empty((T, c.hidden_size), dtype=torch.float32 if precision in ("fp32_residual", "f16_operands") else opd, device=device)
+        store.update(cap=T, policy=precision, h=h, x=mk(c.hidden_size), qkv=mk(qkv_w), ctx=mk(c.num_attention_heads * c.head_dim))
+        # last_hidden_state stays bf16 in every policy (the pooling kernels' input; one rounding of the final RMSNorm, averaged over the
+        # sequence by the pooling: 3e-7 of 1 - cos, profiles/r05_precision_budget.json "only_out_bf16")
+        if out_rows:
+            store.update(xo=store["x"] if opd == BF16 else torch.empty((T, c.hidden_size), dtype=BF16, device=device))
+        if c.num_local_experts:           # every token visits two experts: 2T rows of expert activations
+            store.update(act2=torch.empty((2 * T, c.intermediate_size), dtype=opd, device=device),
+                         y2=torch.empty((2 * T, c.hidden_size), dtype=opd, device=device))
+        else:
+            store.update(act=mk(c.intermediate_size))
+    return {k: (v[:2 * T] if k in ("act2", "y2") else v[:T]) for k, v in store.items() if k not in ("cap", "policy")}
+
+
+def swiglu_mlp(x, h, ws, wgu, wdown, swiglu_epi: int):
+    """h += down(silu(gate(x)) * up(x)); ``swiglu_epi``: the epilogue that matches the row order of ``wgu`` (interleaved or stacked)"""
+    ops.gemm_nt(x, wgu, out=ws["act"], epilogue=swiglu_epi)
+    ops.gemm_nt(ws["act"], wdown, out=h, epilogue=epi_residual(h), residual=h)
+
+
+def moe_experts(x, h, ws, route, w13, w2, swiglu_epi: int):
+    """h += the weighted sum of every token's two experts, on the token-sorted rows of ``route`` (ops.moe_route / moe_route_f32)"""
+    _, weights, counts, row_token, rows = route
+    T = x.shape[0]
+    ops.gemm_nt_grouped(x, w13, counts, 2 * T, out=ws["act2"], epilogue=swiglu_epi, a_rows=row_token)
+    ops.gemm_nt_grouped(ws["act2"], w2, counts, 2 * T, out=ws["y2"])
+    ops.moe_combine(ws["y2"], rows, weights, h, out=h)
+
+
+def attention_half(c: EncoderConfig, g: Geometry, h, ln1, wqkv, wo, ln2, x1, qkv, ctx, x2, rope, h_mid=None, lse=None, kv=None, on_qkv=None):
+    """MistralDecoderLayer.forward up to the MLP (scripts/modeling_mistral_gritlm.py:738-790): h_mid = h + o_proj(attn(rope(qkv(norm1(h))))),
+    x2 = norm2(h_mid), on the rows ``g`` describes.  ``h_mid`` defaults to h itself (the stream updated in place); ``lse`` receives the
+    log-sum-exp rows the backward reads; ``kv``: the layer's (k, v) cache of the cached form, appended to before the attention;
+    ``on_qkv`` sees the rotated q|k|v rows."""
+    nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
+    ops.rmsnorm(h, ln1, eps, out=x1)
+    ops.gemm_nt_rope(x1, wqkv, rope[0], rope[1], (nq + nkv) * d, S=0 if g.pos is not None else g.S, positions=g.pos, out=qkv)    # RoPE in the epilogue
+    if on_qkv is not None:
+        on_qkv(qkv)
+    if g.form == "padded":
+        ops.attn_bidir(qkv, g.bits, g.B, g.S, nq, nkv, d, out=ctx, lse=lse, causal=g.causal, window=g.window)
+    elif g.form == "packed":
+        ops.attn_bidir_varlen(qkv, g.cu, g.max_len, nq, nkv, d, out=ctx, lse=lse, causal=g.causal, window=g.window)
+    else:
+        ops.kv_append_chunk(qkv, kv[0], kv[1], g.lens, g.plen, nq, nkv, d)
+        ops.attn_prefill_cached(qkv, kv[0], kv[1], g.lens, g.plen, nq, nkv, d, out=ctx)
+    h_mid = h if h_mid is None else h_mid
+    ops.gemm_nt(ctx, wo, out=h_mid, epilogue=epi_residual(h), residual=h)
+    ops.rmsnorm(h_mid, ln2, eps, out=x2)
+
+
+def run_layers(c: EncoderConfig, g: Geometry, ws: dict, table, ids, layers, rope, mlp, norm=None, out=None, rows=None, inputs_embeds=None,
+               on_qkv=None):
+    """The no-grad forward on the workspace ``ws``: embedding rows of ``ids`` (or ``inputs_embeds``) -> every layer of ``layers``, an
+    iterable of (ln1, wqkv, wo, ln2, L, kv) -- the attention half's operands in the policy's format, and what ``mlp(L, x, h, ws)``
+    (h += MLP(x), the owner's weight layout) is called with -> the residual stream, of ``rows`` only when given, through the final
+    RMSNorm ``norm`` into ``out`` when given."""
+    h, x = ws["h"], ws["x"]
+    if inputs_embeds is not None:
+        h.copy_(inputs_embeds.to(h.device).reshape(g.T, c.hidden_size))
+    else:
+        ops.embed_gather(table, ids, out=h)
+    for ln1, wqkv, wo, ln2, L, kv in layers:
+        attention_half(c, g, h, ln1, wqkv, wo, ln2, x, ws["qkv"], ws["ctx"], x, rope, kv=kv, on_qkv=on_qkv)
+        mlp(L, x, h, ws)
+    if rows is not None:
+        h = h.index_select(0, rows)
+    return h if norm is None else ops.rmsnorm(h, norm, c.rms_norm_eps, out=out)
+
+
 class _Layer:
     __slots__ = ("wqkv", "wo", "wgu", "wdown", "ln1", "ln2", "wgate", "w13", "w2", "h16")     # h16: fp16 copies (wqkv, wo, wgu, wdown), built on first use
 
@@ -197,9 +351,7 @@ class MistralEncoderEngine:
         values; what is not exact is COUNTED: |w| < 2^-14 becomes subnormal (absolute error <= 3e-8), |w| >= 65520 would become inf and is
         refused.  The copies are keyed on the sources' storage and version counters: weights reloaded or updated in place are converted again."""
         src = (L.wqkv, L.wo, L.w13, L.w2) if self.cfg.num_local_experts else (L.wqkv, L.wo, L.wgu, L.wdown)
-        key = tuple((w.data_ptr(), w._version) for w in src)
-        h = getattr(L, "h16", None)
-        if h is None or h[0] != key:
+        def convert():
             st = self.f16_weight_stats or {"subnormal": 0, "overflow": 0, "total": 0}
             out = []
             for w in src:
@@ -214,8 +366,9 @@ class MistralEncoderEngine:
             if st["overflow"]:
                 raise GritHipError(f"precision='{self.precision}': {st['overflow']} weights exceed the fp16 range (|w| >= 65520)")
             self.f16_weight_stats = st
-            L.h16 = h = (key, tuple(out))
-        return h[1]
+            return tuple(out)
+        L.h16 = keyed(getattr(L, "h16", None), tuple((w.data_ptr(), w._version) for w in src), convert)
+        return L.h16[1]
 
     def f16_overflowed(self, clear: bool = True) -> bool:
         """True when a kernel of an fp16 policy produced a value beyond the fp16 range on this engine's device since the last clear (waits
@@ -230,18 +383,6 @@ class MistralEncoderEngine:
                                "the embeddings of this call are invalid -- run this model with "
                                + ("precision='f16_operands' (fp32 residual stream), " if self.precision == "f16_stream" else "")
                                + "precision='fp32_residual' or 'bf16'")
-
-    def _embed_table(self):
-        """embed_tokens in the residual stream's format: bf16 (also the source of the exact widening into an fp32 stream), or an fp16 copy
-        (262 MB at V 32000) for the fp16 stream, converted on first use"""
-        if self.precision != "f16_stream":
-            return self.embed
-        key = (self.embed.data_ptr(), self.embed._version, tuple(self.embed.shape))
-        if getattr(self, "_embed16", None) is None or self._embed16[0] != key:       # (re-converted when the table is reloaded / updated in place)
-            if bool((self.embed.abs() >= 65520.0).any()):
-                raise GritHipError("precision='f16_stream': embedding weights exceed the fp16 range")
-            self._embed16 = (key, self.embed.to(F16))
-        return self._embed16[1]
 
     # ------------------------------------------------------------------ weights
     @classmethod
@@ -353,55 +494,26 @@ class MistralEncoderEngine:
 
     # ------------------------------------------------------------------ buffers
     def _workspace(self, T: int):
-        """Activation buffers for T token rows: one allocation sized for the largest T seen, handed out as row-slices
-        (ragged / packed batches change T every call)."""
-        cap = self._ws.get("cap", 0)
-        if cap and self._ws.get("policy") != self.precision:
-            cap = 0                       # the precision policy changed: the residual stream / the operands have another dtype
-        if cap < T:
-            c, dev = self.cfg, self.device
-            qkv_w = (c.num_attention_heads + 2 * c.num_key_value_heads) * c.head_dim
-            self._ws.clear()
-            opd = F16 if self.precision in F16_POLICIES else BF16
-            mk = lambda n: torch.empty((T, n), dtype=opd, device=dev)
-            h = torch.empty((T, c.hidden_size), dtype=torch.float32 if self.residual_fp32 else opd, device=dev)
-            self._ws.update(cap=T, policy=self.precision, h=h, x=mk(c.hidden_size), qkv=mk(qkv_w), ctx=mk(c.num_attention_heads * c.head_dim))
-            # last_hidden_state stays bf16 in every policy (the pooling kernels' input; one rounding of the final RMSNorm, averaged over the
-            # sequence by the pooling: 3e-7 of 1 - cos, profiles/r05_precision_budget.json "only_out_bf16")
-            self._ws.update(xo=self._ws["x"] if opd == BF16 else torch.empty((T, c.hidden_size), dtype=BF16, device=dev))
-            if c.num_local_experts:           # every token visits two experts: 2T rows of expert activations
-                self._ws.update(act2=torch.empty((2 * T, c.intermediate_size), dtype=opd, device=dev),
-                                y2=torch.empty((2 * T, c.hidden_size), dtype=opd, device=dev))
-            else:
-                self._ws.update(act=mk(c.intermediate_size))
-        return {k: (v[:2 * T] if k in ("act2", "y2") else v[:T]) for k, v in self._ws.items() if k not in ("cap", "policy")}
+        return workspace(self._ws, self.cfg, self.device, T, self.precision, out_rows=True)
 
     def _mlp(self, L: _Layer, x: torch.Tensor, h: torch.Tensor, ws: dict):
         """h += MLP(x) in place (x = post-attention RMSNorm output): dense SwiGLU MLP or Mixtral's sparse-MoE block."""
         if not self.cfg.num_local_experts:
             _, _, wgu, wdown = self._weights(L)
-            ops.gemm_nt(x, wgu, out=ws["act"], epilogue=EPI_SWIGLU)
-            ops.gemm_nt(ws["act"], wdown, out=h, epilogue=self._epi_res(), residual=h)
-            return
-        T = x.shape[0]
+            return swiglu_mlp(x, h, ws, wgu, wdown, EPI_SWIGLU)
         if self.precision == "f16_operands":
             # the routing decision in fp32 on the residual stream itself (post-attention RMSNorm folded in: nothing rounded), the experts on
             # fp16 operands, the weighted sum added into the fp32 stream
             _, _, w13, w2 = self._f16_weights(L)
-            experts, weights, counts, row_token, rows = ops.moe_route_f32(h, L.ln2, self.cfg.rms_norm_eps, L.wgate)
+            route = ops.moe_route_f32(h, L.ln2, self.cfg.rms_norm_eps, L.wgate)
         else:
             if self.residual_fp32:
                 raise GritHipError("native encoder: precision='fp32_residual' is built for the dense (Mistral) MLP only")
             w13, w2 = L.w13, L.w2
-            experts, weights, counts, row_token, rows = ops.moe_route(x, L.wgate)
+            route = ops.moe_route(x, L.wgate)
         if self.record_routing is not None:
-            self.record_routing.append(experts.clone())
-        ops.gemm_nt_grouped(x, w13, counts, 2 * T, out=ws["act2"], epilogue=EPI_SWIGLU, a_rows=row_token)
-        ops.gemm_nt_grouped(ws["act2"], w2, counts, 2 * T, out=ws["y2"])
-        ops.moe_combine(ws["y2"], rows, weights, h, out=h)
-
-    def _epi_res(self) -> int:
-        return EPI_RESIDUAL_F32 if self.residual_fp32 else EPI_RESIDUAL
+            self.record_routing.append(route[0].clone())
+        moe_experts(x, h, ws, route, w13, w2, EPI_SWIGLU)
 
     def _weights(self, L: _Layer):
         """(wqkv, wo, wgu, wdown) in the operand format of the current policy"""
@@ -415,11 +527,23 @@ class MistralEncoderEngine:
 
     def _rope_tables(self, S: int):
         rounded = self.rope_bf16 and self.precision not in F16_POLICIES    # fp16 operands: the unrounded fp32 tables (fp32 rotation)
-        t = self._rope.get((S, rounded))
-        if t is None:
-            t = rope_tables(S, self.cfg.head_dim, self.cfg.rope_theta, rounded, self.device)
-            self._rope[(S, rounded)] = t
-        return t
+        return cached_rope_tables(self._rope, self.cfg, S, rounded, self.device)
+
+    def _recheck_policy(self):
+        if self.precision in F16_POLICIES:
+            self.set_precision(self.precision)        # (re-checks the model kind the policy is built for)
+
+    def _embed_table(self):
+        """embed_tokens in the residual stream's format: bf16 (also the source of the exact widening into an fp32 stream) or the fp16 copy"""
+        if self.precision != "f16_stream":
+            return self.embed
+        self._embed16 = embed_table_f16(getattr(self, "_embed16", None), self.embed)
+        return self._embed16[1]
+
+    def _run(self, g: Geometry, ws: dict, ids, layers, rope_len: int, **tail):
+        """run_layers on this engine's weights under its policy; ``layers``: (layer, its K/V cache or None) pairs"""
+        return run_layers(self.cfg, g, ws, None if ids is None else self._embed_table(), ids,
+                          ((L.ln1, *self._weights(L)[:2], L.ln2, L, kv) for L, kv in layers), self._rope_tables(rope_len), self._mlp, **tail)
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -438,46 +562,23 @@ class MistralEncoderEngine:
         ``layer_range=(a, b)`` runs decoder layers a .. b-1 only and ``final_norm=False`` returns the residual stream itself: together they
         push a GIVEN hidden state through chosen layers -- the teacher-forced per-layer parity of the Mixtral leg (tools/mixtral_bench.py)."""
         c = self.cfg
-        if inputs_embeds is not None:
-            B, S = inputs_embeds.shape[:2]
-        else:
-            B, S = input_ids.shape
-        T = B * S
-        window = self._window(S)
+        B, S = inputs_embeds.shape[:2] if inputs_embeds is not None else input_ids.shape
         ids = None if inputs_embeds is not None else input_ids.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
         if attention_mask is None:
             attention_mask = torch.ones((B, S), dtype=torch.int64, device=self.device)
-        mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
-        if self.precision in F16_POLICIES:
-            self.set_precision(self.precision)        # (re-checks the model kind / attention mode the policy is built for)
-        ws = self._workspace(T)
-        h, x, qkv, ctx, xo = ws["h"], ws["x"], ws["qkv"], ws["ctx"], ws["xo"]
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        cos, sin = self._rope_tables(S)
-        bits = ops.mask_pack(mask)
-        if inputs_embeds is not None:
-            h.copy_(inputs_embeds.to(self.device).reshape(T, c.hidden_size))
-        else:
-            ops.embed_gather(self._embed_table(), ids, out=h)
-        kv = []
-        for L in (self.layers if layer_range is None else self.layers[layer_range[0]:layer_range[1]]):
-            wqkv, wo = self._weights(L)[:2]
-            ops.rmsnorm(h, L.ln1, eps, out=x)
-            ops.gemm_nt_rope(x, wqkv, cos, sin, (nq + nkv) * d, S=S, out=qkv)         # q/k/v projections + RoPE in the epilogue
-            if return_kv:
-                kvw = qkv.view(B, S, nq + 2 * nkv, d)
-                kdt = qkv.dtype if kv_dtype is None else kv_dtype
-                kv.append((kvw[:, :, nq:nq + nkv].permute(0, 2, 1, 3).to(kdt).contiguous(),
-                           kvw[:, :, nq + nkv:].permute(0, 2, 1, 3).to(kdt).contiguous()))
-            ops.attn_bidir(qkv, bits, B, S, nq, nkv, d, out=ctx, causal=self.causal, window=window)
-            ops.gemm_nt(ctx, wo, out=h, epilogue=self._epi_res(), residual=h)
-            ops.rmsnorm(h, L.ln2, eps, out=x)
-            self._mlp(L, x, h, ws)
-        if final_norm:
-            ops.rmsnorm(h, self.norm, eps, out=xo)
-            out = xo.view(B, S, c.hidden_size)
-        else:
-            out = h.view(B, S, c.hidden_size)
+        self._recheck_policy()
+        g = Geometry.padded(attention_mask.to(device=self.device, dtype=torch.int64).contiguous(), self.causal, self._window(S))
+        ws = self._workspace(g.T)
+        nq, nkv, kv = c.num_attention_heads, c.num_key_value_heads, []
+
+        def capture(qkv):
+            kvw = qkv.view(B, S, nq + 2 * nkv, c.head_dim)
+            kdt = qkv.dtype if kv_dtype is None else kv_dtype
+            kv.append((kvw[:, :, nq:nq + nkv].permute(0, 2, 1, 3).to(kdt).contiguous(),
+                       kvw[:, :, nq + nkv:].permute(0, 2, 1, 3).to(kdt).contiguous()))
+        layers = self.layers if layer_range is None else self.layers[layer_range[0]:layer_range[1]]
+        out = self._run(g, ws, ids, ((L, None) for L in layers), S, norm=self.norm if final_norm else None, out=ws["xo"],
+                        inputs_embeds=inputs_embeds, on_qkv=capture if return_kv else None).view(B, S, c.hidden_size)
         out = out if borrow else out.clone()
         return (out, kv) if return_kv else out
 
@@ -499,33 +600,18 @@ class MistralEncoderEngine:
         if c.num_local_experts:
             raise NotImplementedError("forward_on_cache: sparse-MoE (Mixtral) prefill on a cache is not built")
         B, P = input_ids.shape
-        T = B * P
         Lmax = cache[0][0].shape[2]
         if self.causal and 0 < self.window_keys < Lmax:
             raise NotImplementedError("forward_on_cache: full causal attention over the cache only (window_keys = 0)")
-        if self.precision in F16_POLICIES:
-            self.set_precision(self.precision)
+        self._recheck_policy()
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
-        ws = self._workspace(T)
-        h, x, qkv, ctx = ws["h"], ws["x"], ws["qkv"], ws["ctx"]
-        if cache[0][0].dtype != qkv.dtype:
-            raise TypeError(f"forward_on_cache: the cache holds {cache[0][0].dtype}, precision '{self.precision}' writes {qkv.dtype} K/V")
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        cos, sin = self._rope_tables(Lmax)
-        ops.embed_gather(self._embed_table(), ids, out=h)
-        for L, (ck, cv) in zip(self.layers, cache):
-            wqkv, wo = self._weights(L)[:2]
-            ops.rmsnorm(h, L.ln1, eps, out=x)
-            ops.gemm_nt_rope(x, wqkv, cos, sin, (nq + nkv) * d, positions=positions, out=qkv)
-            ops.kv_append_chunk(qkv, ck, cv, lens, plen, nq, nkv, d)
-            ops.attn_prefill_cached(qkv, ck, cv, lens, plen, nq, nkv, d, out=ctx)
-            ops.gemm_nt(ctx, wo, out=h, epilogue=self._epi_res(), residual=h)
-            ops.rmsnorm(h, L.ln2, eps, out=x)
-            self._mlp(L, x, h, ws)
-        hl = h.index_select(0, last)
-        if not final_norm:
-            return hl
-        return ops.rmsnorm(hl, self.norm, eps, out=torch.empty((B, c.hidden_size), dtype=BF16, device=self.device))
+        ws = self._workspace(B * P)
+        kdt = ws["qkv"].dtype
+        if cache[0][0].dtype != kdt:
+            raise TypeError(f"forward_on_cache: the cache holds {cache[0][0].dtype}, precision '{self.precision}' writes {kdt} K/V")
+        g = Geometry("cached", B, P, B * P, pos=positions, lens=lens, plen=plen, causal=True)
+        return self._run(g, ws, ids, zip(self.layers, cache), Lmax, rows=last, norm=self.norm if final_norm else None,
+                         out=torch.empty((B, c.hidden_size), dtype=BF16, device=self.device))
 
     # ------------------------------------------------------------------ packed (un-padded) forward
     @staticmethod
@@ -546,59 +632,25 @@ class MistralEncoderEngine:
         HOST tensors (what the tokenizer returns) are the preferred input: the batch geometry -- right-padded or not, row lengths,
         cu_seqlens, the packed token list -- is then derived on the host, only real tokens cross PCIe, and the call issues its launches
         without a single device synchronisation (the host runs ahead: the next batch is tokenised, and in-process multi-GPU encode
-        feeds the other replicas, while this one computes).  Device tensors take the same path with three small syncs."""
-        c = self.cfg
-        B, S = input_ids.shape
-        window = self._window(S)
+        feeds the other replicas, while this one computes).  Device tensors take the same path: one transfer decides the layout, and the two
+        gathers by the mask (positions, token ids) synchronise as well."""
+        S = input_ids.shape[1]
         with torch.cuda.device(self.device):
-            if attention_mask.device.type == "cpu" and input_ids.device.type == "cpu":
-                m = attention_mask != 0
-                lens_h = m.sum(dim=1)
-                if packed is None:
-                    packed = bool(((torch.arange(S).unsqueeze(0) < lens_h.unsqueeze(1)) == m).all()) and bool((lens_h > 0).all())
-                if packed:
-                    pids = input_ids.to(torch.int64)[m].contiguous().to(self.device, non_blocking=True)
-                    pos = torch.arange(S, dtype=torch.int32).unsqueeze(0).expand(B, S)[m].contiguous().to(self.device, non_blocking=True)
-                    cu_h = torch.zeros((B + 1,), dtype=torch.int32)
-                    cu_h[1:] = torch.cumsum(lens_h, dim=0)
-                    cu = cu_h.to(self.device, non_blocking=True)
-                    T, max_len = int(cu_h[-1]), int(lens_h.max())
-            else:
+            if attention_mask.device.type != "cpu" or input_ids.device.type != "cpu":
                 attention_mask = attention_mask.to(device=self.device, dtype=torch.int64)
                 input_ids = input_ids.to(device=self.device, dtype=torch.int64)
-                if packed is None:
-                    packed = self.is_right_padded(attention_mask) and bool((attention_mask.sum(dim=1) > 0).all())
-                if packed:
-                    lens = attention_mask.sum(dim=1).to(torch.int32)
-                    cu = torch.zeros((B + 1,), dtype=torch.int32, device=self.device)
-                    cu[1:] = torch.cumsum(lens, dim=0)
-                    keep = attention_mask.bool()
-                    pids = input_ids[keep].contiguous()                              # row-major order == sequence order
-                    pos = (torch.arange(S, device=self.device, dtype=torch.int32).unsqueeze(0).expand(B, S))[keep].contiguous()
-                    T, max_len = int(pids.numel()), int(lens.max().item())
+            g = None if packed is False else Geometry.from_mask(attention_mask, packed, self.device, self.causal, self._window(S))
             if instr_len is not None:
                 instr_len = instr_len.to(self.device)
-            if not packed:
+            if g is None:
                 mask = attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
                 h = self.forward(input_ids.to(device=self.device, dtype=torch.int64), mask, borrow=True)
                 return ops.pool_norm(h, mask, method, normalize, instr_len)
-            if self.precision in F16_POLICIES:
-                self.set_precision(self.precision)
-            ws = self._workspace(T)
-            h, x, qkv, ctx, xo = ws["h"], ws["x"], ws["qkv"], ws["ctx"], ws["xo"]
-            nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-            cos, sin = self._rope_tables(S)
-            ops.embed_gather(self._embed_table(), pids, out=h)
-            for L in self.layers:
-                wqkv, wo = self._weights(L)[:2]
-                ops.rmsnorm(h, L.ln1, eps, out=x)
-                ops.gemm_nt_rope(x, wqkv, cos, sin, (nq + nkv) * d, positions=pos, out=qkv)
-                ops.attn_bidir_varlen(qkv, cu, max_len, nq, nkv, d, out=ctx, causal=self.causal, window=window)
-                ops.gemm_nt(ctx, wo, out=h, epilogue=self._epi_res(), residual=h)
-                ops.rmsnorm(h, L.ln2, eps, out=x)
-                self._mlp(L, x, h, ws)
-            ops.rmsnorm(h, self.norm, eps, out=xo)
-            return ops.pool_norm_varlen(xo, cu, method, normalize, instr_len)
+            self._recheck_policy()
+            ws = self._workspace(g.T)
+            pids = input_ids.to(torch.int64)[g.keep].contiguous().to(self.device, non_blocking=True)
+            xo = self._run(g, ws, pids, ((L, None) for L in self.layers), S, norm=self.norm, out=ws["xo"])
+            return ops.pool_norm_varlen(xo, g.cu, method, normalize, instr_len)
 
     def flops_per_token(self, S: int) -> float:
         """Algorithmic forward FLOPs per token: projections + MLP + attention core."""

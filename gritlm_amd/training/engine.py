@@ -19,8 +19,9 @@ import os
 import torch
 
 from .. import ops
-from .._lib import EPI_RESIDUAL, EPI_RESIDUAL_F32, EPI_STORE, EPI_SWIGLU_BWD, EPI_SWIGLU_STACKED, EPI_SWIGLU_STACKED_SAVE, GritHipError
-from ..encoder import F16_POLICIES, EncoderConfig, rope_tables, sliding_window_keys
+from .._lib import EPI_RESIDUAL, EPI_STORE, EPI_SWIGLU_BWD, EPI_SWIGLU_STACKED, EPI_SWIGLU_STACKED_SAVE, GritHipError
+from ..encoder import (F16_POLICIES, EncoderConfig, Geometry, attention_half, cached_rope_tables, embed_table_f16, keyed, moe_experts, run_layers,
+                       sliding_window_keys, swiglu_mlp, workspace)
 
 BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 
@@ -38,42 +39,6 @@ class _LayerParams:
 class SavedForward:
     """Everything pass 2 keeps from the forward of one chunk."""
     __slots__ = ("ids", "mask", "geom", "B", "S", "layers", "h_final", "x_final", "router")
-
-
-class _Geometry:
-    """Row layout of one chunk.  Padded: T = B*S rows, key-padding bitmask.  Packed: only the real tokens of a right-padded
-    batch (rows of sequence b at [cu[b], cu[b+1])), per-row RoPE positions -- GEMMs, norms and attention never see padding
-    (the reference computes every padded position)."""
-    __slots__ = ("packed", "B", "S", "T", "bits", "cu", "pos", "max_len", "keep", "causal", "window")
-
-    @staticmethod
-    def padded(mask: torch.Tensor):
-        g = _Geometry()
-        g.packed, (g.B, g.S), g.causal, g.window = False, mask.shape, False, 0
-        g.T = g.B * g.S
-        g.bits = ops.mask_pack(mask)
-        g.cu = g.pos = g.keep = None
-        g.max_len = g.S
-        return g
-
-    @staticmethod
-    def from_mask(mask: torch.Tensor):
-        """Packed geometry when the mask is right-padded with no empty row, else None."""
-        B, S = mask.shape
-        keep = mask != 0
-        lens = keep.sum(dim=1)
-        ar = torch.arange(S, device=mask.device)
-        # one host sync decides the layout: (right-padded?, no empty rows?, longest row, number of tokens)
-        ok, max_len, T = torch.stack([(((ar.unsqueeze(0) < lens.unsqueeze(1)) == keep).all() & (lens > 0).all()).to(torch.int64),
-                                      lens.max(), lens.sum()]).tolist()
-        if not ok:
-            return None
-        g = _Geometry()
-        g.packed, g.B, g.S, g.T, g.max_len, g.keep, g.bits, g.causal, g.window = True, B, S, int(T), int(max_len), keep, None, False, 0
-        g.cu = torch.zeros((B + 1,), dtype=torch.int32, device=mask.device)
-        g.cu[1:] = torch.cumsum(lens, dim=0)
-        g.pos = ar.to(torch.int32).unsqueeze(0).expand(B, S)[keep].contiguous()
-        return g
 
 
 class MistralTrainEngine:
@@ -242,82 +207,27 @@ class MistralTrainEngine:
     def _f16_weights(self, li: int):
         """fp16 copies of layer li's packed GEMM weights (wqkv, wo, [gate; up] stacked, down) -- exact for 6.1e-5 <= |w| < 65520, refused
         beyond -- converted when first needed after an optimizer update (14.5 GB for the 7B shape: ~10 ms of a 50 s step)."""
-        ver = tuple(p._version for p in self._all_owners(li))
-        hit = self._w16.get(li)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        L = self.layers[li]
-        out = []
-        for w in (L.wqkv, L.wo, L.wgu, L.wdown):
-            w16 = w.data.to(F16)
-            for part in (w16 if w16.dim() == 3 else (w16,)):            # (slice by slice: an expert stack is 12 GB)
-                if bool(torch.isinf(part).any()):
-                    raise GritHipError(f"nograd_precision='{self.nograd_precision}': weights of layer {li} exceed the fp16 range")
-            out.append(w16)
-        self._w16[li] = (ver, tuple(out))
+        def convert():
+            L = self.layers[li]
+            out = []
+            for w in (L.wqkv, L.wo, L.wgu, L.wdown):
+                w16 = w.data.to(F16)
+                for part in (w16 if w16.dim() == 3 else (w16,)):            # (slice by slice: an expert stack is 12 GB)
+                    if bool(torch.isinf(part).any()):
+                        raise GritHipError(f"nograd_precision='{self.nograd_precision}': weights of layer {li} exceed the fp16 range")
+                out.append(w16)
+            return tuple(out)
+        self._w16[li] = keyed(self._w16.get(li), tuple(p._version for p in self._all_owners(li)), convert)
         return self._w16[li][1]
 
-    def _mlp_fwd_f16(self, li: int, L, x2, h, ws, w16):
-        """h += down(silu(gate(x2)) * up(x2)) on fp16 operands (x2 fp16; h the fp32 / fp16 residual stream, updated in place)."""
-        _, _, wgu, wdown = w16
-        ops.gemm_nt(x2, wgu, out=ws["act"], epilogue=EPI_SWIGLU_STACKED)
-        ops.gemm_nt(ws["act"], wdown, out=h, epilogue=EPI_RESIDUAL_F32 if h.dtype == F32 else EPI_RESIDUAL, residual=h)
-
-    def _ws16_buffers(self, T: int, stream_dtype):
-        c = self.cfg
-        cap = self._ws16.get("cap", 0)
-        if cap < T or self._ws16.get("sdt") != stream_dtype:
-            self._ws16.clear()
-            nq, nkv, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
-            mk = lambda n, dt=F16, rows=T: torch.empty((rows, n), dtype=dt, device=self.device)
-            r = 2 if c.num_local_experts else 1
-            self._ws16.update(cap=T, sdt=stream_dtype, h=mk(c.hidden_size, stream_dtype), x=mk(c.hidden_size), qkv=mk((nq + 2 * nkv) * d),
-                              ctx=mk(nq * d), act=mk(c.intermediate_size, F16, r * T))
-            if c.num_local_experts:
-                self._ws16.update(y=mk(c.hidden_size, F16, 2 * T))
-        return {k: (v[:2 * T] if k == "y" or (k == "act" and c.num_local_experts) else v[:T]) for k, v in self._ws16.items() if k not in ("cap", "sdt")}
-
-    def _forward_nograd_f16(self, ids, geom, B, S):
-        """The no-grad forward under an fp16-operand policy: the encoder engine's data flow (gritlm_amd/encoder.py) on this engine's packed
-        parameters.  Returns last_hidden_state rows [T,H] bf16 (the pooling kernels' input; one rounding of the final RMSNorm)."""
-        c, pol = self.cfg, self.nograd_precision
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        T = geom.T
-        t = self._rope.get((S, "f32"))
-        if t is None:
-            t = self._rope[(S, "f32")] = rope_tables(S, d, c.rope_theta, False, self.device)      # unrounded tables: the rotation runs in fp32
-        cos, sin = t
-        ws = self._ws16_buffers(T, F32 if pol == "f16_operands" else F16)
-        h, x, qkv, ctx = ws["h"], ws["x"], ws["qkv"], ws["ctx"]
-        if pol == "f16_stream":
-            key = (self.embed.data_ptr(), self.embed._version)
-            if self._embed16 is None or self._embed16[0] != key:
-                self._embed16 = (key, self.embed.data.to(F16))
-            ops.embed_gather(self._embed16[1], ids, out=h)
-        else:
-            ops.embed_gather(self.embed.data, ids, out=h)
-        epi = EPI_RESIDUAL_F32 if h.dtype == F32 else EPI_RESIDUAL
-        for li, L in enumerate(self.layers):
-            w16 = self._f16_weights(li)
-            ops.rmsnorm(h, L.ln1.data, eps, out=x)
-            if geom.packed:
-                ops.gemm_nt_rope(x, w16[0], cos, sin, (nq + nkv) * d, positions=geom.pos, out=qkv)
-                ops.attn_bidir_varlen(qkv, geom.cu, geom.max_len, nq, nkv, d, out=ctx, causal=geom.causal, window=geom.window)
-            else:
-                ops.gemm_nt_rope(x, w16[0], cos, sin, (nq + nkv) * d, S=S, out=qkv)
-                ops.attn_bidir(qkv, geom.bits, B, S, nq, nkv, d, out=ctx, causal=geom.causal, window=geom.window)
-            ops.gemm_nt(ctx, w16[1], out=h, epilogue=epi, residual=h)
-            ops.rmsnorm(h, L.ln2.data, eps, out=x)
-            self._mlp_fwd_f16(li, L, x, h, ws, w16)
-        return ops.rmsnorm(h, self.norm.data, eps, out=torch.empty((T, c.hidden_size), dtype=BF16, device=self.device))
+    def _mlp_nograd_f16(self, li: int, x2, h, ws):
+        """h += down(silu(gate(x2)) * up(x2)) on the fp16 copies of layer li's stacked [gate; up] and down weights (the ``mlp`` of the
+        encoder's layer loop, which the fp16 no-grad forward runs through)"""
+        swiglu_mlp(x2, h, ws, *self._f16_weights(li)[2:], EPI_SWIGLU_STACKED)
 
     # ------------------------------------------------------------------ helpers
     def _rope_tables(self, S):
-        t = self._rope.get(S)
-        if t is None:
-            t = rope_tables(S, self.cfg.head_dim, self.cfg.rope_theta, self.rope_bf16, self.device)
-            self._rope[S] = t
-        return t
+        return cached_rope_tables(self._rope, self.cfg, S, self.rope_bf16, self.device)
 
     def _transposed_act(self, x: torch.Tensor, tag: str) -> torch.Tensor:
         """x [T,N] -> x^T in a zero-padded [N, T rounded up to 128] buffer (K operand of the wgrad GEMM)."""
@@ -378,25 +288,14 @@ class MistralTrainEngine:
         """MistralDecoderLayer.forward (scripts/modeling_mistral_gritlm.py:738-790) on the kernels.  ``need_bwd``: also produce what
         backward() reads (log-sum-exp rows, the pre-activation gate|up, a separate h_mid); otherwise SwiGLU is fused into the gate|up
         GEMM's epilogue (stacked-weight form) and the residual stream is updated in place."""
-        c = self.cfg
-        nq, nkv, d, eps = c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.rms_norm_eps
-        T, dev = geom.T, self.device
+        nq = self.cfg.num_attention_heads
         x1, qkv, ctx, x2 = buf["x1"], buf["qkv"], buf["ctx"], buf["x2"]
-        ops.rmsnorm(h, L.ln1.data, eps, out=x1)
-        if geom.packed:
-            lse = torch.empty((T, nq), dtype=F32, device=dev) if need_bwd else None
-            ops.gemm_nt_rope(x1, L.wqkv, cos, sin, (nq + nkv) * d, positions=geom.pos, out=qkv)      # q/k/v projections + RoPE epilogue
-            ops.attn_bidir_varlen(qkv, geom.cu, geom.max_len, nq, nkv, d, out=ctx, lse=lse, causal=geom.causal, window=geom.window)
-        else:
-            lse = torch.empty((B, nq, S), dtype=F32, device=dev) if need_bwd else None
-            ops.gemm_nt_rope(x1, L.wqkv, cos, sin, (nq + nkv) * d, S=S, out=qkv)
-            ops.attn_bidir(qkv, geom.bits, B, S, nq, nkv, d, out=ctx, lse=lse, causal=geom.causal, window=geom.window)
+        lse = torch.empty((geom.T, nq) if geom.packed else (B, nq, S), dtype=F32, device=self.device) if need_bwd else None
         if need_bwd:
             h_mid = buf["h_mid"]
         else:                            # h must survive when it is a saved layer input (recompute policy) -> h_out doubles as h_mid
             h_mid = h_out if h_out is not None else h
-        ops.gemm_nt(ctx, L.wo.data, out=h_mid, epilogue=EPI_RESIDUAL, residual=h)
-        ops.rmsnorm(h_mid, L.ln2.data, eps, out=x2)
+        attention_half(self.cfg, geom, h, L.ln1.data, L.wqkv, L.wo.data, L.ln2.data, x1, qkv, ctx, x2, (cos, sin), h_mid=h_mid, lse=lse)
         if h_out is None:
             h_out = h_mid
         sv = dict(h_in=h, x1=x1, qkv=qkv, ctx=ctx, lse=lse, h_mid=h_mid, x2=x2, h_out=h_out)
@@ -413,11 +312,10 @@ class MistralTrainEngine:
         B, S = input_ids.shape
         dev = self.device
         mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous()
-        geom = _Geometry.from_mask(mask) if packed else None
+        window = int(self.window_keys) if causal and 0 < self.window_keys < S else 0
+        geom = Geometry.from_mask(mask, causal=bool(causal), window=window) if packed else None
         if geom is None:
-            geom = _Geometry.padded(mask)
-        geom.causal = bool(causal)
-        geom.window = int(self.window_keys) if causal and 0 < self.window_keys < S else 0
+            geom = Geometry.padded(mask, bool(causal), window)
         ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
         ids = ids[geom.keep].contiguous() if geom.packed else ids.view(-1)
         T = geom.T
@@ -426,7 +324,17 @@ class MistralTrainEngine:
         saved = SavedForward()
         saved.ids, saved.mask, saved.geom, saved.B, saved.S, saved.layers = ids, mask, geom, B, S, []
         if not save and self.nograd_precision in F16_POLICIES and self._router_log is None:
-            xf = self._forward_nograd_f16(ids, geom, B, S)
+            # the encoder engine's layer loop on fp16 copies of this engine's packed parameters; last_hidden_state rows bf16 (the pooling
+            # kernels' input; one rounding of the final RMSNorm), the unrounded RoPE tables (the rotation runs in fp32)
+            pol = self.nograd_precision
+            layers = ((L.ln1.data, *self._f16_weights(li)[:2], L.ln2.data, li, None) for li, L in enumerate(self.layers))
+            table = self.embed.data
+            if pol == "f16_stream":
+                self._embed16 = embed_table_f16(self._embed16, self.embed)
+                table = self._embed16[1]
+            xf = run_layers(c, geom, workspace(self._ws16, c, dev, T, pol, out_rows=False), table, ids, layers,
+                            cached_rope_tables(self._rope, c, S, False, dev), self._mlp_nograd_f16, norm=self.norm.data,
+                            out=torch.empty((T, H), dtype=BF16, device=dev))
             return (xf if geom.packed else xf.view(B, S, H)), saved
         cos, sin = self._rope_tables(S)
         mk = lambda n: torch.empty((T, n), dtype=BF16, device=dev)
@@ -653,15 +561,12 @@ class MixtralTrainEngine(MistralTrainEngine):
             buf["h_mid"] = torch.empty((T, c.hidden_size), dtype=BF16, device=self.device)
         return buf
 
-    def _mlp_fwd_f16(self, li: int, L, x2, h, ws, w16):
+    def _mlp_nograd_f16(self, li: int, x2, h, ws):
         """The sparse-MoE block of the fp16 no-grad forward ("f16_operands": h is the fp32 residual stream): routing in fp32 on h itself
         (post-attention RMSNorm folded in), experts on fp16 copies of the fused gate_up_proj / down_proj, combine into the fp32 stream."""
-        T = x2.shape[0]
-        _, _, wgu, wdown = w16
-        experts, weights, counts, row_token, rows = ops.moe_route_f32(h, L.ln2.data, self.cfg.rms_norm_eps, L.wgate.data)
-        ops.gemm_nt_grouped(x2, wgu, counts, 2 * T, out=ws["act"], epilogue=EPI_SWIGLU_STACKED, a_rows=row_token)
-        ops.gemm_nt_grouped(ws["act"], wdown, counts, 2 * T, out=ws["y"])
-        ops.moe_combine(ws["y"], rows, weights, h, out=h)
+        L = self.layers[li]
+        route = ops.moe_route_f32(h, L.ln2.data, self.cfg.rms_norm_eps, L.wgate.data)
+        moe_experts(x2, h, ws, route, *self._f16_weights(li)[2:], EPI_SWIGLU_STACKED)
 
     def _mlp_fwd(self, L, h_mid, x2, buf, need_bwd: bool, h_out):
         T = x2.shape[0]

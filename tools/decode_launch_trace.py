@@ -12,17 +12,15 @@ Uses only the decoder's public surface (MistralDecoder, generate, its documented
 """
 import argparse
 import hashlib
-import inspect
 import json
 import os
 import sys
-import types
 
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from gritlm_amd import ops  # noqa: E402
+sys.path[:0] = [os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), os.path.dirname(os.path.abspath(__file__))]
 from gritlm_amd.decoder import MistralDecoder  # noqa: E402
+from launch_recorder import Recorder, canonical  # noqa: E402
 
 BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 FUSE = ("deferred", "deferred_mlp", "all", "qkv", "none")
@@ -87,36 +85,8 @@ class _Engine:
 def trace(fuse="deferred", B=1, f16=False, experts=0, engine="bf16", cached=True, prefill="rows", attrs=None, gen=None):
     """(launch list, last_prefill) of one generate() call.  ``engine``: the stand-in engine's policy (the decoder is pinned to bf16 / f16 by
     ``f16``); ``cached``: the prompt rides on a cached prefix of S0 tokens; ``attrs``: decoder attributes to set; ``gen``: generate() keywords."""
-    out, names, keep = [], {}, []
-
-    def label(t):
-        if isinstance(t, torch.Tensor):
-            keep.append(t)                              # (alive to the end: a freed buffer's address would be handed out again)
-            n = names.setdefault(t.untyped_storage().data_ptr(), len(names))
-            return ["T", n, t.storage_offset(), list(t.shape), list(t.stride()), str(t.dtype)]
-        if isinstance(t, (list, tuple)):
-            return [label(x) for x in t]
-        return t if t is None or isinstance(t, (bool, int, float, str)) else str(t)
-
-    def log(name, args, kw):
-        out.append([name, [label(x) for x in args], {k: label(v) for k, v in sorted(kw.items())}])
-
-    def rec(name, ret=None):
-        sig = inspect.signature(saved[name])
-
-        def f(*a, **k):
-            full = sig.bind(*a, **k)                    # every argument of the op by name, defaults filled in: what the launch receives,
-            full.apply_defaults()                       # however the call site spelled it
-            log(name, [], full.arguments)
-            return ret(*a, **k) if ret else full.arguments.get("out")
-        return f
-
-    saved = {n: v for n, v in vars(ops).items() if isinstance(v, types.FunctionType) and not n.startswith("_") and v.__module__ == ops.__name__}
-    for n in saved:
-        setattr(ops, n, rec(n))
-    ops.attn_decode_workspace = rec("attn_decode_workspace", lambda *a, **k: torch.zeros(8))
-    ops.f16_overflow_flag = rec("f16_overflow_flag", lambda *a, **k: False)
-    try:
+    with Recorder({"attn_decode_workspace": lambda *a, **k: torch.zeros(8), "f16_overflow_flag": lambda *a, **k: False}) as r:
+        out, log = r.out, r.log
         eng = _Engine(experts, engine, log)
         c = eng.cfg
         dec = MistralDecoder(eng, torch.zeros((c.vocab, c.hidden_size), dtype=BF16))
@@ -130,9 +100,6 @@ def trace(fuse="deferred", B=1, f16=False, experts=0, engine="bf16", cached=True
         dec.generate(torch.zeros((B, P), dtype=torch.int64), NEW, past_key_values=past, **(gen or {}))
         log("engine.after", [], dict(precision=eng.precision, causal=eng.causal))          # (the policy generate() leaves behind)
         return out, dec.last_prefill
-    finally:
-        for n, v in saved.items():
-            setattr(ops, n, v)
 
 
 def cases():
@@ -160,10 +127,6 @@ def cases():
         m[f"prefill_gemm/B3/{p}/engine_same"] = dict(B=3, f16=f16, engine="f16_operands" if f16 else "bf16", prefill="gemm")
     m["moe/sample/B2/bf16"] = dict(B=2, experts=4, gen=dict(do_sample=True, seed=5))
     return m
-
-
-def canonical(tr) -> str:
-    return json.dumps(tr, sort_keys=True, separators=(",", ":"))
 
 
 def launches(tr) -> int:
