@@ -104,41 +104,14 @@ __device__ __forceinline__ int wrow_of(int wc, int j) {
     __builtin_amdgcn_s_barrier();            \
     GRIT_SEG_FENCE();                        \
   } while (0)
-// K-loop barriers.  Default (round 2/3): two per phase -- load segment | B | 16 MFMAs | B -- with the second wave group one barrier
-// behind, so every barrier interval has one group in its MFMAs and the other in its load segment.  -DGRIT_GEMM_BAR1: ONE per phase,
-// group 0 takes it in FRONT of its MFMAs and group 1 BEHIND them:
-//     group 0:  L(p) | B(p) | M(p)  L(p+1) | B(p+1) | ...          group 1:  L(p) M(p) | B(p) | L(p+1) M(p+1) | B(p+1) | ...
-// so in every interval group 0's MFMAs still sit beside group 1's load segment and the other way round, but the matrix pipe changes
-// hands at a barrier only every other time (the mid-interval hand-over needs no rendezvous).  The hazards hold unchanged: what L(p)
-// reads was waited for by every wave (counted vmcnt at the end of its L(p-1)) in front of B(p-1), and L(p) runs behind B(p-1) in both
-// groups; a slot's last reads (phase q) are complete (lgkmcnt(0) at the top of M(q)) in front of B(q+1) in both groups, and the DMA
-// that refills it is issued in L(p), p >= q + 2, behind B(p-1).
-#ifdef GRIT_GEMM_BAR1
-#define GRIT_BAR_PRE()                                 \
-  do {                                                 \
-    GRIT_SEG_FENCE();                                  \
-    if (wr == 0) __builtin_amdgcn_s_barrier();         \
-    GRIT_SEG_FENCE();                                  \
-  } while (0)
-#define GRIT_BAR_POST()                                \
-  do {                                                 \
-    GRIT_SEG_FENCE();                                  \
-    if (wr == 1) __builtin_amdgcn_s_barrier();         \
-    GRIT_SEG_FENCE();                                  \
-  } while (0)
-#define GRIT_STAGGER(G) do { } while (0)
-#else
+// K-loop barriers: two per phase -- load segment | B | 16 MFMAs | B -- with the second wave group one barrier behind (GRIT_STAGGER), so
+// every barrier interval has one group in its MFMAs and the other in its load segment.  The barrier BEHIND a segment is executed inside
+// GRIT_MMA, in front of the segment's last product; what is left behind the segment is the compiler fence.
+// Rejected: ONE barrier per phase (group 0 in front of its products, group 1 behind them), 0.964-0.988x -- without the mid-interval
+// rendezvous the two groups' products run beside each other and the pipe idles at the end of the interval (profiles/r04_gemm_barrier_ab.log).
 #define GRIT_BAR_PRE() GRIT_BARRIER()
-#define GRIT_BAR_POST() GRIT_BARRIER()
+#define GRIT_BAR_POST() GRIT_SEG_FENCE()
 #define GRIT_STAGGER(G) do { if (wr == (G)) GRIT_BARRIER(); } while (0)
-#endif
-
-// A/B builds only (tools/ubench): -DGRIT_SWIGLU_BWD_DIRECT keeps the direct (row-per-lane) epilogue for SWIGLU_BWD
-#ifdef GRIT_SWIGLU_BWD_DIRECT
-#define GRIT_SWB_DIRECT(EPI) ((EPI) == GRIT_EPI_SWIGLU_BWD)
-#else
-#define GRIT_SWB_DIRECT(EPI) false
-#endif
 #ifdef GRIT_GEMM_STAMP
 // debug build only (tools/ubench/gemm_stamp.cpp): shader-clock stamps of two waves (one per wave group) of a few workgroups at the
 // seams of the persistent tile loop
@@ -189,9 +162,9 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
   // ---- tile of block v: XCD-aware id (bijective remap, guide T1) + grouped ordering (GM m-tiles per group): the 32 workgroups an
   //      XCD runs at a time are 32 consecutive tile ids = 4 m-tiles x 8 n-tiles sharing A / W panels in that XCD's 4 MiB L2.  The
   //      sharing lives on the tiles of an XCD staying IN STEP (the L2 holds about two K-tiles of the XCD's traffic): one workgroup per
-  //      tile keeps them in step (equal tile times, in-order dispatch); a persistent one-workgroup-per-CU variant with the K-tile stream
-  //      running through the tile boundaries was built in round 2 -- bit-identical, +3 % in isolation, equal in the model (the chip is
-  //      power-limited) at TWICE the L2-miss traffic because its CUs drift apart -- and removed (profiles/r02_gemm_persistent_*.log).
+  //      tile keeps them in step (equal tile times, in-order dispatch), and so does the persistent form, whose CUs draw from one queue
+  //      per XCD (described at the top of this file and at the tile loop below; a persistent form with a STATIC tile list per CU drifted
+  //      apart and doubled the L2-miss traffic, profiles/r02_gemm_persistent_*.log).
   //      PERSIST: v = 8 * (index in the XCD's queue) + XCD, the same numbering one workgroup per tile would have.
   const int n_virtual = PERSIST ? tiles_m * tiles_n : (int)gridDim.x;
   const int group_sz = GM * tiles_n;
@@ -368,10 +341,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
         // MFMAs.  With the folded form the accumulators were not live at the top of the first K-tile, hipcc packed other values into
         // their registers and then SPILLED one 16-byte accumulator fragment in phase 1 -- its scratch reload (vmcnt(0): a full drain of
         // the LDS-DMA queue) sat in the middle of phase 2's MFMAs, once per tile, in every variant but RoPE / RESIDUAL.  Opaque: 0 spills,
-        // 0 scratch in all seven persistent instantiations (tools/kernel_resources.py).  -DGRIT_GEMM_FOLDED_ZERO: the old form (A/B).
-#ifndef GRIT_GEMM_FOLDED_ZERO
+        // 0 scratch in all persistent instantiations (tools/kernel_resources.py; profiles/r03_gemm_ab_opaque_zero.log).
         if (PERSIST) asm volatile("" : "+v"(acc[i][j]));
-#endif
       }
   };
   zero_acc();
@@ -385,26 +356,13 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
   _Pragma("unroll") for (int ii = 0; ii < 4; ++ii)                                                    \
     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                  \
       xf[ii][ks] = *reinterpret_cast<const frag_t*>((SB) + a_off + (H) * HALF_BYTES + ii * 2048 + s_off[ks])
-// The barrier BEHIND an MFMA segment is executed GRIT_GEMM_BAR_EARLY products before the segment's end (round 4; default 1, i.e. in
-// front of the LAST product).  That barrier only hands the matrix pipe to the other wave group -- this wave's LDS reads completed at
-// the top of the segment and the products touch registers only, so every hazard rule above holds with the barrier anywhere inside the
-// segment -- and the other group's wake-up (barrier release -> lgkmcnt(0) -> s_setprio -> first v_mfma) now overlaps this group's last
-// product instead of following it.  Same-box interleaved A/B against the barrier behind the segment (-DGRIT_GEMM_BAR_EARLY=0), outputs
-// bit-identical on all 29 harness cases: q|k|v (RoPE) 1.024-1.025x, o_proj 1.020-1.026x, gate|up 1.010x, down 1.012-1.016x on two boxes;
-// 2 products early 0.92-0.94x (the two groups' products interleave and the finishing wave's load segment starts late; with the tail at
-// s_setprio 3: 1.006-1.018x), 3: 1.00-1.01x, 6: 0.97-0.99x.  The opposite change -- ONE barrier per phase, group 0 in front of its
-// products and group 1 behind them (-DGRIT_GEMM_BAR1) -- is 0.964-0.988x: without the mid-interval rendezvous a group that finishes its
-// load segment early issues its products BESIDE the other group's, and the pipe then idles at the end of the interval while the
-// other group loads alone.  profiles/r04_gemm_barrier_ab.log.
-#ifndef GRIT_GEMM_BAR_EARLY
-#define GRIT_GEMM_BAR_EARLY 1
-#endif
-#if GRIT_GEMM_BAR_EARLY > 0 && !defined(GRIT_GEMM_BAR1)
-#ifdef GRIT_GEMM_BAR_TAILPRIO
-#define GRIT_TAIL_PRIO() __builtin_amdgcn_s_setprio(GRIT_GEMM_BAR_TAILPRIO)
-#else
-#define GRIT_TAIL_PRIO() do { } while (0)
-#endif
+// The barrier BEHIND an MFMA segment is executed in front of the segment's LAST product (round 4): it only hands the matrix pipe to the
+// other wave group -- this wave's LDS reads completed at the top of the segment and the products touch registers only, so every hazard
+// rule above holds with the barrier anywhere inside the segment -- and the other group's wake-up (barrier release -> lgkmcnt(0) ->
+// s_setprio -> first v_mfma) overlaps this group's last product instead of following it.  Same-box interleaved A/B against the barrier
+// behind the segment, bit-identical: q|k|v (RoPE) 1.024-1.025x, o_proj 1.020-1.026x, gate|up 1.010x, down 1.012-1.016x.  Rejected: 2
+// products early 0.92-0.94x (1.006-1.018x with the tail at s_setprio 3), 3: 1.00-1.01x, 6: 0.97-0.99x; profiles/r04_gemm_barrier_ab.log.
+  constexpr int BAR_AT = 14;                                       // index of the product the barrier follows (16 products per segment)
 #define GRIT_MMA(WF, I0, J0)                                                                          \
   do {                                                                                                \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                \
@@ -414,43 +372,17 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
       const int ks = q_ >> 3, ii = (q_ >> 1) & 3, jj = q_ & 1;                                        \
       acc[(I0) + ii][(J0) + jj] =                                                                     \
           mma16(WF[jj][ks], xf[ii][ks], acc[(I0) + ii][(J0) + jj]);                                   \
-      if (q_ == 15 - (GRIT_GEMM_BAR_EARLY)) {                                                         \
-        GRIT_BARRIER();                                                                               \
-        GRIT_TAIL_PRIO();                                                                             \
-      }                                                                                               \
+      if (q_ == BAR_AT) GRIT_BARRIER();                                                               \
     }                                                                                                 \
     __builtin_amdgcn_s_setprio(0);                                                                    \
   } while (0)
-#undef GRIT_BAR_POST
-#define GRIT_BAR_POST() GRIT_SEG_FENCE()
-#else
-#define GRIT_MMA(WF, I0, J0)                                                                          \
-  do {                                                                                                \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-    __builtin_amdgcn_s_setprio(1);                                                                    \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                  \
-      _Pragma("unroll") for (int ii = 0; ii < 4; ++ii)                                                \
-        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                                              \
-          acc[(I0) + ii][(J0) + jj] =                                                                 \
-              mma16(WF[jj][ks], xf[ii][ks], acc[(I0) + ii][(J0) + jj]);                                   \
-    __builtin_amdgcn_s_setprio(0);                                                                    \
-  } while (0)
-#endif
   // load segment: the LDS reads are issued ahead of the two LDS-DMA instructions, then the counted wait:
   // vmcnt(8) = "all but the 4 newest half-tiles have landed"
   // WAIT: 1 = the counted wait; 2 = drain; 3 = the counted wait unless `skip_waits` (a wave-uniform run-time flag: ONE copy of the
   // first K-tile's code serves the first tile of a workgroup and the tiles that follow an epilogue -- two copies made hipcc spill a
   // fragment at their join, and a spill reload inside the K loop is a vmcnt(0))
-#ifdef GRIT_GEMM_LGKM_PRE   /* A/B: the fragment reads are waited for (and the priority raised) in FRONT of the barrier that starts the MFMA segment */
-#define GRIT_LSEG_TAIL()                                         \
-  do {                                                           \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           \
-    __builtin_amdgcn_s_setprio(1);                               \
-  } while (0)
-#else
-#define GRIT_LSEG_TAIL() do { } while (0)
-#endif
+  // (Rejected: waiting for the fragment reads and raising the priority in FRONT of the barrier that starts the MFMA segment;
+  //  profiles/r04_gemm_barrier_ab.log.)
 #define GRIT_LSEG_END(NREADS, WAIT)                                                                   \
   do {                                                                                                \
     __builtin_amdgcn_sched_group_barrier(0x100, NREADS, 0);                                           \
@@ -458,7 +390,6 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
     if constexpr ((WAIT) == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                       \
     if constexpr ((WAIT) == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       \
     if constexpr ((WAIT) == 3) { if (!skip_waits) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }  \
-    GRIT_LSEG_TAIL();                                                                                 \
   } while (0)
 
   // One K-tile = 4 phases, one output quadrant (16 MFMAs) each.  Half-tile stream (issue order):
@@ -533,7 +464,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // W_h0(0), A_h0(0)
   GRIT_BARRIER();
   GRIT_READ_W(wf0[0], 0, smem);
-  GRIT_STAGGER(1);                    // the second wave group runs one barrier behind the first (BAR1: no stagger in the count)
+  GRIT_STAGGER(1);                    // the second wave group runs one barrier behind the first
 
   // F16: the overflow bits of a tile are published at the END OF ITS EPILOGUE and the accumulator word cleared, so that it is not live
   // across the K loop (in the persistent form one more live VGPR there pushed the RESIDUAL instantiation over the 256-register cliff:
@@ -546,15 +477,19 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
       ovf_acc = 0;                                                         \
     }                                                                      \
   } while (0)
-  // ---- epilogue: lane holds C[m][n..n+3], m = frag row base + (lane&15), n = frag col base + (lane>>4)*4
+  // ---- two epilogues, each instantiated only for the cases it serves: the full-width ones (STORE, RESIDUAL, RESIDUAL_F32, SWIGLU_BWD) turn
+  //      their rows through LDS (epilogue_lds, below), RoPE and the SwiGLU forwards store directly (why: the figures behind epilogue_lds)
+  constexpr bool LDS_EPI = (EPI == GRIT_EPI_STORE || EPI == GRIT_EPI_RESIDUAL || EPI == GRIT_EPI_SWIGLU_BWD || EPI == GRIT_EPI_RESIDUAL_F32);
+  // ---- direct epilogue: lane holds C[m][n..n+3], m = frag row base + (lane&15), n = frag col base + (lane>>4)*4
   auto wrow = [&](int j) { return wrow_of<ROPE>(wc, j); };
   auto epilogue = [&](int64_t m0, int64_t M, int n0) {
+  if constexpr (!LDS_EPI) {
   int ln_e = lane;
   if (PERSIST) asm volatile("" : "+v"(ln_e));               // per-lane output coordinates are rebuilt per tile, not carried through the K loop
   const int frow = ln_e & 15, kq = ln_e >> 4;
   const int64_t mrow = m0 + wr * 128 + frow;
   const int ncol = n0 + wc * 64 + kq * 4;
-  // The 8 row blocks of the lane go out in batches of RB: all table / residual loads of a batch are issued up front, so the epilogue pays
+  // The 8 row blocks of the lane go out in batches of RB: all table loads of a batch are issued up front, so the epilogue pays
   // one memory latency per batch.  One workgroup per tile: one batch (the K loop's registers are dead).  PERSIST: the K loop's state
   // stays live across the epilogue, smaller batches keep it out of scratch memory.
   constexpr int RB = !PERSIST ? 8 : (ROPE ? 2 : 8);
@@ -588,17 +523,6 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
         }
       }
     }
-  }
-  uint4 rpre[8][2];
-  if constexpr (EPI == GRIT_EPI_RESIDUAL) {
-#pragma unroll
-    for (int i = ib; i < ib + RB; ++i)
-#pragma unroll
-      for (int jq = 0; jq < 2; ++jq) {
-        const int64_t m = mrow + i * 16;
-        const int n = n0 + wrow(2 * jq + (kq & 1)) + (kq >> 1) * 8;
-        rpre[i][jq] = (m < M && n < N) ? *reinterpret_cast<const uint4*>(Rsd + m * ldr + n) : make_uint4(0, 0, 0, 0);
-      }
   }
 #pragma unroll
   for (int i = ib; i < ib + RB; ++i) {
@@ -653,8 +577,8 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
       }
     } else {
       // 16-byte stores: v_permlane16_swap exchanges the 16-lane rows of two adjacent n-fragments so that every lane ends up with
-      // 8 CONSECUTIVE columns (rows 0/2 of the wave keep fragment j, rows 1/3 take fragment j+1) -- half the store (and residual
-      // load) instructions of the natural 4-columns-per-lane layout; the store tail is issue-bound (guide T21)
+      // 8 CONSECUTIVE columns (rows 0/2 of the wave keep fragment j, rows 1/3 take fragment j+1) -- half the store
+      // instructions of the natural 4-columns-per-lane layout; the store tail is issue-bound (guide T21)
 #pragma unroll
       for (int jp = 0; jp < 4; jp += 2) {
         f32x4_t lo = acc[i][jp], hi4 = acc[i][jp + 1];
@@ -666,34 +590,6 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
         const int n = n0 + wrow(jp + (kq & 1)) + (kq >> 1) * 8;
         if (n >= N) continue;
         float v[8] = {lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-        if constexpr (EPI == GRIT_EPI_RESIDUAL) {
-          // the reference rounds the Linear output to bf16 before the residual add (:769,:775)
-          const uint4 rv = rpre[i][jp >> 1];
-          const uint32_t ra[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const uint32_t rr = pack2_op<F16>(v[2 * e], v[2 * e + 1]);
-            v[2 * e] = lo16_op<F16>(rr) + lo16_op<F16>(ra[e]); v[2 * e + 1] = hi16_op<F16>(rr) + hi16_op<F16>(ra[e]);
-          }
-        }
-        if constexpr (EPI == GRIT_EPI_SWIGLU_BWD) {
-          // d_act = bf16(acc) (what the un-fused path stores and re-reads), then the arithmetic of grit_swiglu_bwd on the saved [gate | up]
-          const uint4 gv = *reinterpret_cast<const uint4*>(Rsd + m * ldr + n), uv = *reinterpret_cast<const uint4*>(Rsd + m * ldr + N + n);
-          const uint32_t ga[4] = {gv.x, gv.y, gv.z, gv.w}, ua[4] = {uv.x, uv.y, uv.z, uv.w};
-          uint32_t og[4], ou[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const uint32_t dd = pack2bf_hw(v[2 * e], v[2 * e + 1]);
-            float dg0, du0, dg1, du1;
-            swiglu_bwd_elem(bflo(dd), bflo(ga[e]), bflo(ua[e]), dg0, du0);
-            swiglu_bwd_elem(bfhi(dd), bfhi(ga[e]), bfhi(ua[e]), dg1, du1);
-            og[e] = pack2bf_hw(dg0, dg1);
-            ou[e] = pack2bf_hw(du0, du1);
-          }
-          *reinterpret_cast<uint4*>(C + m * ldc + n) = make_uint4(og[0], og[1], og[2], og[3]);
-          *reinterpret_cast<uint4*>(C + m * ldc + N + n) = make_uint4(ou[0], ou[1], ou[2], ou[3]);
-          continue;
-        }
         const uint4 pk = make_uint4(pack2_op<F16>(v[0], v[1]), pack2_op<F16>(v[2], v[3]), pack2_op<F16>(v[4], v[5]), pack2_op<F16>(v[6], v[7]));
         if constexpr (F16) ovf_acc |= h2_nonfinite(pk.x) | h2_nonfinite(pk.y) | h2_nonfinite(pk.z) | h2_nonfinite(pk.w);
         *reinterpret_cast<uint4*>(C + m * ldc + n) = pk;
@@ -702,17 +598,19 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
   }
   }
   GRIT_OVF_FLUSH();
+  }  // !LDS_EPI
   };
 
-  // ---- epilogue through LDS (round 3; used by STORE / RESIDUAL, written for RoPE and SwiGLU too).  In the MFMA layout consecutive lanes hold
+  // ---- epilogue through LDS (round 3; STORE, RESIDUAL, RESIDUAL_F32, SWIGLU_BWD).  In the MFMA layout consecutive lanes hold
   //      consecutive ROWS (lane & 15 = row, lane >> 4 = which 16-byte piece), so one 16-byte store (or residual load) instruction
   //      touches 16 rows x 64 B: every lane of a 16-lane pass hits a different cache line -- the epilogue was issue-bound in the texture
   //      path (stamps: 5.6-8.5 k cycles per tile for the stores alone, 17-19 k with the residual loads).  Each wave now turns its row
   //      block (16 rows x 128 B) through a private 4 KiB piece of the staging ring (dead at this point: the A_h1 / W_h1 slots of stage 1)
-  //      and goes to memory with lanes 8 r .. 8 r + 7 on the 8 pieces of ONE row: 8 full 128-byte lines per instruction (RoPE: two 64-byte
-  //      segments per row; SwiGLU: 4 lanes per 64-byte output row).  The arithmetic is untouched -- the residual is added after the
-  //      turn, to the same bf16-rounded value -- so the results are bit-identical to the direct epilogue (tools/ubench/gemm_ab.cpp).
+  //      and goes to memory with lanes 8 r .. 8 r + 7 on the 8 pieces of ONE row: 8 full 128-byte lines per instruction.  The arithmetic
+  //      is untouched -- the residual is added after the turn, to the same bf16-rounded value -- so the results are bit-identical to
+  //      the direct form these epilogues had before (tools/ubench/gemm_ab.cpp).
   auto epilogue_lds = [&](int64_t m0, int64_t M, int n0) {
+  if constexpr (LDS_EPI) {
     int ln_e = lane;
     if (PERSIST) asm volatile("" : "+v"(ln_e));
     const int frow = ln_e & 15, kq = ln_e >> 4;
@@ -791,131 +689,71 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
 #pragma unroll
       for (int i = 0; i < 4; ++i) swb_fetch(i);
     }
-    bool rotate = false;
-    int m0_mod = 0;
-    if constexpr (ROPE) {
-      rotate = n0 + (wc >> 1) * 128 < rope.rope_cols;                           // this wave's head is a q or k head (uniform per wave)
-      m0_mod = (int)(m0 % rope.S);                                              // block-uniform: the only 64-bit division
-    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       if (PERSIST && (i & 1) == 0) __builtin_amdgcn_sched_barrier(0);           // bound the live range of the per-row-block temporaries
-      if constexpr (ROPE) {
-        if (rotate) {
-          const int64_t m = mbase + frow + i * 16;
-          const int64_t mc = m < M ? m : M - 1;
-          const int pos = rope.positions ? rope.positions[mc] : (m0_mod + (int)(mc - m0)) % rope.S;
-#pragma unroll
-          for (int p2 = 0; p2 < 2; ++p2) {
-            const int c1 = (wc & 1) * 32 + p2 * 16 + kq * 4;                     // head-local column of fragment p2, lane's 4 columns
-            const float4 cs = *reinterpret_cast<const float4*>(rope.cos_tab + (int64_t)pos * 64 + c1);
-            const float4 sn = *reinterpret_cast<const float4*>(rope.sin_tab + (int64_t)pos * 64 + c1);
-            const float cc[4] = {cs.x, cs.y, cs.z, cs.w}, ss[4] = {sn.x, sn.y, sn.z, sn.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float x1 = acc[i][p2][r], x2 = acc[i][p2 + 2][r];
-              if constexpr (!F16) {
-                const uint32_t xr = pack2bf_hw(x1, x2);                           // q/k = bf16(linear) first (:655-657)
-                x1 = bflo(xr); x2 = bfhi(xr);
-              }
-              acc[i][p2][r] = rope_lo(x1, x2, cc[r], ss[r]);
-              acc[i][p2 + 2][r] = rope_hi(x1, x2, cc[r], ss[r]);
-            }
-          }
-        }
-      }
       char* xb = xp + (i & 1) * 2048;
-      if constexpr (SWIGLU) {
-        float o0[4], o1[4];
+#pragma unroll
+      for (int jp = 0; jp < 4; jp += 2) {
+        f32x4_t lo = acc[i][jp], hi4 = acc[i][jp + 1];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          if constexpr (F16) {
-            o0[r] = silu_f(acc[i][0][r]) * acc[i][1][r];
-            o1[r] = silu_f(acc[i][2][r]) * acc[i][3][r];
-          } else {
-          const uint32_t gu0 = pack2bf_hw(acc[i][0][r], acc[i][1][r]), gu1 = pack2bf_hw(acc[i][2][r], acc[i][3][r]);
-          const uint32_t ss = pack2bf_hw(silu_f(bflo(gu0)), silu_f(bflo(gu1)));
-          o0[r] = bflo(ss) * bfhi(gu0);
-          o1[r] = bfhi(ss) * bfhi(gu1);
-          }
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(o0[r]), __float_as_uint(o1[r]), false, false);
-          o0[r] = __uint_as_float(sw[0]); o1[r] = __uint_as_float(sw[1]);
+          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(lo[r]), __float_as_uint(hi4[r]), false, false);
+          lo[r] = __uint_as_float(sw[0]); hi4[r] = __uint_as_float(sw[1]);
         }
-        // 16 rows x 64 B (32 output columns of the wave): unit q of the row, swizzled by (row >> 1) & 3
-        const int q = (kq & 1) * 2 + (kq >> 1);
-        const uint4 ov = make_uint4(pack2_op<F16>(o0[0], o0[1]), pack2_op<F16>(o0[2], o0[3]), pack2_op<F16>(o1[0], o1[1]), pack2_op<F16>(o1[2], o1[3]));
+        const int pidx = (jp + (kq & 1)) * 2 + (kq >> 1);                      // 16-byte unit of the row: fragment jp + (kq & 1), half kq >> 1
+        const uint4 ov = make_uint4(pack2_op<F16>(lo[0], lo[1]), pack2_op<F16>(lo[2], lo[3]), pack2_op<F16>(hi4[0], hi4[1]), pack2_op<F16>(hi4[2], hi4[3]));
         if constexpr (F16) ovf_acc |= h2_nonfinite(ov.x) | h2_nonfinite(ov.y) | h2_nonfinite(ov.z) | h2_nonfinite(ov.w);
-        *reinterpret_cast<uint4*>(xb + frow * 64 + ((q ^ ((frow >> 1) & 3)) << 4)) = ov;
-      } else {
-#pragma unroll
-        for (int jp = 0; jp < 4; jp += 2) {
-          f32x4_t lo = acc[i][jp], hi4 = acc[i][jp + 1];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(lo[r]), __float_as_uint(hi4[r]), false, false);
-            lo[r] = __uint_as_float(sw[0]); hi4[r] = __uint_as_float(sw[1]);
-          }
-          const int pidx = (jp + (kq & 1)) * 2 + (kq >> 1);                      // 16-byte unit of the row: fragment jp + (kq & 1), half kq >> 1
-          const uint4 ov = make_uint4(pack2_op<F16>(lo[0], lo[1]), pack2_op<F16>(lo[2], lo[3]), pack2_op<F16>(hi4[0], hi4[1]), pack2_op<F16>(hi4[2], hi4[3]));
-          if constexpr (F16) ovf_acc |= h2_nonfinite(ov.x) | h2_nonfinite(ov.y) | h2_nonfinite(ov.z) | h2_nonfinite(ov.w);
-          *reinterpret_cast<uint4*>(xb + frow * 128 + ((pidx ^ (frow & 7)) << 4)) = ov;
-        }
+        *reinterpret_cast<uint4*>(xb + frow * 128 + ((pidx ^ (frow & 7)) << 4)) = ov;
       }
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_waitcnt(0xC07F);                                       // lgkmcnt(0): the wave's own pieces are in the buffer
       asm volatile("" ::: "memory");
-      if constexpr (SWIGLU) {
-        const int row = ln_e >> 2, unit = ln_e & 3;
-        const uint4 piece = *reinterpret_cast<const uint4*>(xb + row * 64 + ((unit ^ ((row >> 1) & 3)) << 4));
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int row = hh * 8 + tr;
+        uint4 piece = *reinterpret_cast<const uint4*>(xb + row * 128 + ((tu ^ (row & 7)) << 4));
         const int64_t m = mbase + i * 16 + row;
-        const int oc = ((n0 + wc * 64) >> 1) + unit * 8;
-        if (m < M && 2 * oc < N) *reinterpret_cast<uint4*>(C + m * ldc + oc) = piece;
-      } else {
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          const int row = hh * 8 + tr;
-          uint4 piece = *reinterpret_cast<const uint4*>(xb + row * 128 + ((tu ^ (row & 7)) << 4));
-          const int64_t m = mbase + i * 16 + row;
-          if constexpr (EPI == GRIT_EPI_RESIDUAL) {
-            // the reference rounds the Linear output to bf16 before the residual add (:769,:775): `piece` holds the rounded values
-            const uint4 rv = rpre[i][hh];
-            if constexpr (F16) {
-              // fp16 residual stream: f16(acc) + residual as ONE v_pk_add_f16 per pair -- the IEEE fp16 sum of two fp16 values, i.e. exactly
-              // what unpack / fp32 add / round would give, without the unpack temporaries (they spilled 35 VGPRs in the persistent form)
-              piece = make_uint4(pk_add_f16(piece.x, rv.x), pk_add_f16(piece.y, rv.y), pk_add_f16(piece.z, rv.z), pk_add_f16(piece.w, rv.w));
-              ovf_acc |= h2_nonfinite(piece.x) | h2_nonfinite(piece.y) | h2_nonfinite(piece.z) | h2_nonfinite(piece.w);
-            } else {
-            piece = make_uint4(pack2bf_hw(bflo(piece.x) + bflo(rv.x), bfhi(piece.x) + bfhi(rv.x)), pack2bf_hw(bflo(piece.y) + bflo(rv.y), bfhi(piece.y) + bfhi(rv.y)),
-                               pack2bf_hw(bflo(piece.z) + bflo(rv.z), bfhi(piece.z) + bfhi(rv.z)), pack2bf_hw(bflo(piece.w) + bflo(rv.w), bfhi(piece.w) + bfhi(rv.w)));
-            }
+        if constexpr (EPI == GRIT_EPI_RESIDUAL) {
+          // the reference rounds the Linear output to bf16 before the residual add (:769,:775): `piece` holds the rounded values
+          const uint4 rv = rpre[i][hh];
+          if constexpr (F16) {
+            // fp16 residual stream: f16(acc) + residual as ONE v_pk_add_f16 per pair -- the IEEE fp16 sum of two fp16 values, i.e. exactly
+            // what unpack / fp32 add / round would give, without the unpack temporaries (they spilled 35 VGPRs in the persistent form)
+            piece = make_uint4(pk_add_f16(piece.x, rv.x), pk_add_f16(piece.y, rv.y), pk_add_f16(piece.z, rv.z), pk_add_f16(piece.w, rv.w));
+            ovf_acc |= h2_nonfinite(piece.x) | h2_nonfinite(piece.y) | h2_nonfinite(piece.z) | h2_nonfinite(piece.w);
+          } else {
+          piece = make_uint4(pack2bf_hw(bflo(piece.x) + bflo(rv.x), bfhi(piece.x) + bfhi(rv.x)), pack2bf_hw(bflo(piece.y) + bflo(rv.y), bfhi(piece.y) + bfhi(rv.y)),
+                             pack2bf_hw(bflo(piece.z) + bflo(rv.z), bfhi(piece.z) + bfhi(rv.z)), pack2bf_hw(bflo(piece.w) + bflo(rv.w), bfhi(piece.w) + bfhi(rv.w)));
           }
-          if constexpr (EPI == GRIT_EPI_SWIGLU_BWD) {
-            // `piece` = d_act rounded to bf16 (what the un-fused path stores and re-reads), then the arithmetic of grit_swiglu_bwd
-            const uint4 gv = gpre[i & 3][hh], uv = upre[i & 3][hh];
-            const uint32_t da[4] = {piece.x, piece.y, piece.z, piece.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w}, ua[4] = {uv.x, uv.y, uv.z, uv.w};
-            uint32_t og[4], ou[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float dg0, du0, dg1, du1;
-              swiglu_bwd_elem(bflo(da[e]), bflo(ga[e]), bflo(ua[e]), dg0, du0);
-              swiglu_bwd_elem(bfhi(da[e]), bfhi(ga[e]), bfhi(ua[e]), dg1, du1);
-              og[e] = pack2bf_hw(dg0, dg1);
-              ou[e] = pack2bf_hw(du0, du1);
-            }
-            if (m < M && ncol_t < N) {
-              *reinterpret_cast<uint4*>(C + m * ldc + ncol_t) = make_uint4(og[0], og[1], og[2], og[3]);
-              *reinterpret_cast<uint4*>(C + m * ldc + N + ncol_t) = make_uint4(ou[0], ou[1], ou[2], ou[3]);
-            }
-            continue;
-          }
-          if (m < M && ncol_t < N) *reinterpret_cast<uint4*>(C + m * ldc + ncol_t) = piece;
         }
         if constexpr (EPI == GRIT_EPI_SWIGLU_BWD) {
-          if (i + 4 < 8) swb_fetch(i + 4);            // the slot just consumed takes the rows of the block four ahead
+          // `piece` = d_act rounded to bf16 (what the un-fused path stores and re-reads), then the arithmetic of grit_swiglu_bwd
+          const uint4 gv = gpre[i & 3][hh], uv = upre[i & 3][hh];
+          const uint32_t da[4] = {piece.x, piece.y, piece.z, piece.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w}, ua[4] = {uv.x, uv.y, uv.z, uv.w};
+          uint32_t og[4], ou[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float dg0, du0, dg1, du1;
+            swiglu_bwd_elem(bflo(da[e]), bflo(ga[e]), bflo(ua[e]), dg0, du0);
+            swiglu_bwd_elem(bfhi(da[e]), bfhi(ga[e]), bfhi(ua[e]), dg1, du1);
+            og[e] = pack2bf_hw(dg0, dg1);
+            ou[e] = pack2bf_hw(du0, du1);
+          }
+          if (m < M && ncol_t < N) {
+            *reinterpret_cast<uint4*>(C + m * ldc + ncol_t) = make_uint4(og[0], og[1], og[2], og[3]);
+            *reinterpret_cast<uint4*>(C + m * ldc + N + ncol_t) = make_uint4(ou[0], ou[1], ou[2], ou[3]);
+          }
+          continue;
         }
+        if (m < M && ncol_t < N) *reinterpret_cast<uint4*>(C + m * ldc + ncol_t) = piece;
+      }
+      if constexpr (EPI == GRIT_EPI_SWIGLU_BWD) {
+        if (i + 4 < 8) swb_fetch(i + 4);            // the slot just consumed takes the rows of the block four ahead
       }
     }
     GRIT_OVF_FLUSH();
+  }  // LDS_EPI
   };
   // Measured against the direct epilogue on the same box (ratios to the round-2 kernel, M = 131072; profiles/r03_gemm_ab_lds_epilogue.log):
   // RESIDUAL K = 4096 1.019 -> 1.049, K = 14336 1.003 -> 1.011, STORE 1.029 -> 1.039, RoPE 1.026 -> 1.025, SwiGLU 1.027 -> 1.017 (its output
@@ -924,8 +762,6 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
   // at the same moment = 64 MB at ~7 TB/s -- the seam of a lock-stepped launch is an HBM burst, not an issue problem.
   // SWIGLU_BWD (round 3, second half): two 16-byte loads + two 16-byte stores per 8 outputs made the direct form the slowest epilogue of the
   // training step (1135 TF on the d_act GEMM against 1400-1470 for the other dense launches of a chunk); through the turn they are full lines.
-  constexpr bool LDS_EPI = (EPI == GRIT_EPI_STORE || EPI == GRIT_EPI_RESIDUAL || EPI == GRIT_EPI_SWIGLU_BWD || EPI == GRIT_EPI_RESIDUAL_F32) && !GRIT_SWB_DIRECT(EPI);
-
   if constexpr (!PERSIST) {
     for (int kt = 0; kt < nk; kt += 2) {
       ktile(kclamp(kt + 1), kclamp(kt + 2), B0, MID);
@@ -1019,7 +855,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_nt_k(const uint16_t* __restrict
 // Launch knobs for A/B runs (read once, thread-safe static initialisation): GRIT_GEMM_GM=<n> m-tiles per scheduling group (default 4:
 // 4 m x 8 n tiles in flight per XCD), GRIT_GEMM_NOREMAP=1 disables the XCD remap, GRIT_GEMM_RR=1 deals tile groups round-robin to the
 // XCDs for dense launches too (default: grouped launches only), GRIT_GEMM_NOPERSIST=1 always launches one workgroup per tile,
-// GRIT_GEMM_PERSIST_MAXKT=<n> lifts the K-tile bound of the persistent form (default 128).
+// GRIT_GEMM_PERSIST_MAXKT=<n> sets the largest K-tile count that still takes the persistent form (default 1024).
 struct GemmKnobs {
   int gm, remap, rr_all, persist, persist_max_kt;
 };
@@ -1146,16 +982,24 @@ static void ensure_lds_optin(KernelT kernel, std::atomic<uint64_t>& done, int by
   }
 }
 
+// One problem as an entry point describes it (R: the epilogue's second operand -- residual, or the saved [gate | up] of the training epilogues)
+struct GemmProblem {
+  const void *A, *W;
+  void* C;
+  const void* R;
+  int64_t M;
+  int N, K;
+  int64_t lda, ldw, ldc, ldr;
+};
+
 template <int EPI, bool F16 = false>
-static int launch_gemm(const void* A, const void* W, void* C, const void* R, int64_t M, int N, int K, int64_t lda, int64_t ldw,
-                       int64_t ldc, int64_t ldr, hipStream_t st, GemmGroups grp = GemmGroups{nullptr, nullptr, 0, 0},
-                       GemmRope rope = GemmRope{nullptr, nullptr, nullptr, 0, 0}) {
+static int launch_gemm(const GemmProblem& p, hipStream_t st, const GemmGroups& grp, const GemmRope& rope) {
   unsigned int* ovf = nullptr;
   if constexpr (F16) {
     ovf = f16_flag_ptr();
     GRIT_REQUIRE(ovf != nullptr, GRIT_E_LAUNCH, "grit_gemm_f16_nt: the overflow flag word of this device is not reachable");
   }
-  const int tiles_m = grp.counts ? (int)(M / BM) + grp.n_groups : (int)((M + BM - 1) / BM), tiles_n = (N + BN - 1) / BN;
+  const int tiles_m = grp.counts ? (int)(p.M / BM) + grp.n_groups : (int)((p.M + BM - 1) / BM), tiles_n = (p.N + BN - 1) / BN;
   static std::atomic<uint64_t> optin{0}, optin_p{0};
   const GemmKnobs& kn = gemm_knobs();
   // grouped launches: round-robin tile groups over the XCDs (remap 2) on a grid rounded up to 8 x whole groups
@@ -1168,44 +1012,195 @@ static int launch_gemm(const void* A, const void* W, void* C, const void* R, int
   // K = 14336, where the seam is only 3 % of a tile, and was bounded to <= 128 K-tiles; without the per-tile queue drain it wins there
   // too: down_proj 1.013x at M = 131072, 1.042x at a training chunk, the gate|up weight gradient (K = 16384 tokens) 1.031x, bit-identical;
   // profiles/r03_gemm_ab_opaque_zero.log.  GRIT_GEMM_PERSIST_MAXKT restores a bound for A/B runs.)
-  const int n_cu = device_cu_count();
-  const bool off32 = 256 * lda * 2 + 128 < (1ll << 32) && (int64_t)N * ldw * 2 + 128 < (1ll << 32);     // PERSIST's 32-bit source offsets
-  if (kn.persist && !rr && grp.counts == nullptr && (K / BK) % 2 == 0 && K / BK >= 4 && K / BK <= kn.persist_max_kt && (int64_t)tiles_m * tiles_n >= 2 * (int64_t)n_cu &&
+  const int n_cu = device_cu_count(), nk = p.K / BK;
+  const bool off32 = 256 * p.lda * 2 + 128 < (1ll << 32) && (int64_t)p.N * p.ldw * 2 + 128 < (1ll << 32);     // PERSIST's 32-bit source offsets
+  if (kn.persist && !rr && grp.counts == nullptr && nk % 2 == 0 && nk >= 4 && nk <= kn.persist_max_kt && (int64_t)tiles_m * tiles_n >= 2 * (int64_t)n_cu &&
       n_cu % 8 == 0 && off32) {
     unsigned int* ctr = next_counter_set(st);
     if (ctr != nullptr) {
       ensure_lds_optin(gemm_bf16_nt_k<EPI, true, F16>, optin_p, PERSIST_LDS_BYTES);
-      hipLaunchKernelGGL((gemm_bf16_nt_k<EPI, true, F16>), dim3((unsigned)n_cu), dim3(512), PERSIST_LDS_BYTES, st, (const uint16_t*)A,
-                         (const uint16_t*)W, (uint16_t*)C, (const uint16_t*)R, M, N, K, lda, ldw, ldc, ldr, tiles_m, tiles_n, kn.gm,
-                         remap_mode, grp, rope, ctr, GemmSecond{}, ovf);
+      hipLaunchKernelGGL((gemm_bf16_nt_k<EPI, true, F16>), dim3((unsigned)n_cu), dim3(512), PERSIST_LDS_BYTES, st, (const uint16_t*)p.A,
+                         (const uint16_t*)p.W, (uint16_t*)p.C, (const uint16_t*)p.R, p.M, p.N, p.K, p.lda, p.ldw, p.ldc, p.ldr, tiles_m, tiles_n,
+                         kn.gm, remap_mode, grp, rope, ctr, GemmSecond{}, ovf);
       GRIT_CHECK_LAUNCH("grit_gemm_bf16_nt (persistent)");
       return GRIT_OK;
     }
     (void)hipGetLastError();          // no counter set (symbol lookup / memset refused, e.g. inside a stream capture): per-tile launch
   }
   ensure_lds_optin(gemm_bf16_nt_k<EPI, false, F16>, optin, 2 * STAGE_BYTES);
-  hipLaunchKernelGGL((gemm_bf16_nt_k<EPI, false, F16>), dim3(nblocks), dim3(512), 2 * STAGE_BYTES, st, (const uint16_t*)A, (const uint16_t*)W,
-                     (uint16_t*)C, (const uint16_t*)R, M, N, K, lda, ldw, ldc, ldr, tiles_m, tiles_n, kn.gm, remap_mode, grp, rope,
-                     (unsigned int*)nullptr, GemmSecond{}, ovf);
+  hipLaunchKernelGGL((gemm_bf16_nt_k<EPI, false, F16>), dim3(nblocks), dim3(512), 2 * STAGE_BYTES, st, (const uint16_t*)p.A,
+                     (const uint16_t*)p.W, (uint16_t*)p.C, (const uint16_t*)p.R, p.M, p.N, p.K, p.lda, p.ldw, p.ldc, p.ldr, tiles_m, tiles_n, kn.gm,
+                     remap_mode, grp, rope, (unsigned int*)nullptr, GemmSecond{}, ovf);
   GRIT_CHECK_LAUNCH("grit_gemm_bf16_nt");
   return GRIT_OK;
 }
 
 template <int EPI>
-static int launch_gemm_pair(const void* A1, const void* W1, void* C1, const void* R1, int64_t M1, int N1, int64_t lda1, int64_t ldw1,
-                            int64_t ldc1, int64_t ldr1, const void* A2, const void* W2, void* C2, const void* R2, int64_t M2, int N2,
-                            int64_t lda2, int64_t ldw2, int64_t ldc2, int64_t ldr2, int K, hipStream_t st) {
-  const int tm1 = (int)((M1 + BM - 1) / BM), tn1 = (N1 + BN - 1) / BN, tm2 = (int)((M2 + BM - 1) / BM), tn2 = (N2 + BN - 1) / BN;
+static int launch_gemm_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t st) {
+  const int tm1 = (int)((p1.M + BM - 1) / BM), tn1 = (p1.N + BN - 1) / BN, tm2 = (int)((p2.M + BM - 1) / BM), tn2 = (p2.N + BN - 1) / BN;
   static std::atomic<uint64_t> optin{0};
   const GemmKnobs& kn = gemm_knobs();
-  const GemmSecond sec{(const uint16_t*)A2, (const uint16_t*)W2, (uint16_t*)C2, (const uint16_t*)R2, M2, lda2, ldw2, ldc2, ldr2, N2, tm2, tn2, tm1 * tn1};
+  const GemmSecond sec{(const uint16_t*)p2.A, (const uint16_t*)p2.W, (uint16_t*)p2.C, (const uint16_t*)p2.R, p2.M, p2.lda, p2.ldw, p2.ldc, p2.ldr,
+                       p2.N, tm2, tn2, tm1 * tn1};
   ensure_lds_optin(gemm_bf16_nt_k<EPI, false>, optin, 2 * STAGE_BYTES);
-  hipLaunchKernelGGL((gemm_bf16_nt_k<EPI, false>), dim3((unsigned)(tm1 * tn1 + tm2 * tn2)), dim3(512), 2 * STAGE_BYTES, st, (const uint16_t*)A1,
-                     (const uint16_t*)W1, (uint16_t*)C1, (const uint16_t*)R1, M1, N1, K, lda1, ldw1, ldc1, ldr1, tm1, tn1, kn.gm, 1,
-                     GemmGroups{nullptr, nullptr, 0, 0}, GemmRope{nullptr, nullptr, nullptr, 0, 0}, (unsigned int*)nullptr, sec,
-                     (unsigned int*)nullptr);
+  hipLaunchKernelGGL((gemm_bf16_nt_k<EPI, false>), dim3((unsigned)(tm1 * tn1 + tm2 * tn2)), dim3(512), 2 * STAGE_BYTES, st, (const uint16_t*)p1.A,
+                     (const uint16_t*)p1.W, (uint16_t*)p1.C, (const uint16_t*)p1.R, p1.M, p1.N, p1.K, p1.lda, p1.ldw, p1.ldc, p1.ldr, tm1, tn1,
+                     kn.gm, 1, GemmGroups{}, GemmRope{}, (unsigned int*)nullptr, sec, (unsigned int*)nullptr);
   GRIT_CHECK_LAUNCH("grit_gemm_bf16_nt_pair");
   return GRIT_OK;
+}
+
+// The launchers, instantiated HERE and in this order -- each is the per-tile and the persistent kernel of one (epilogue, operand format):
+// the 28 kernels tests/test_kernel_resources.py counts.  The order is the order of the kernels in the code object, which a change of the
+// host code below then cannot move (a device-side diff of two revisions stays readable).
+#define GRIT_GEMM_INSTANCE(EPI, F16) template int launch_gemm<EPI, F16>(const GemmProblem&, hipStream_t, const GemmGroups&, const GemmRope&)
+GRIT_GEMM_INSTANCE(GRIT_EPI_STORE, false);
+GRIT_GEMM_INSTANCE(GRIT_EPI_SWIGLU, false);
+GRIT_GEMM_INSTANCE(GRIT_EPI_SWIGLU_STACKED, false);
+GRIT_GEMM_INSTANCE(GRIT_EPI_SWIGLU_STACKED_SAVE, false);
+GRIT_GEMM_INSTANCE(GRIT_EPI_SWIGLU_BWD, false);
+GRIT_GEMM_INSTANCE(GRIT_EPI_ROPE, false);
+template int launch_gemm_pair<GRIT_EPI_RESIDUAL>(const GemmProblem&, const GemmProblem&, hipStream_t);
+GRIT_GEMM_INSTANCE(GRIT_EPI_RESIDUAL, false);
+GRIT_GEMM_INSTANCE(GRIT_EPI_RESIDUAL_F32, false);
+GRIT_GEMM_INSTANCE(GRIT_EPI_STORE, true);
+GRIT_GEMM_INSTANCE(GRIT_EPI_RESIDUAL, true);
+GRIT_GEMM_INSTANCE(GRIT_EPI_RESIDUAL_F32, true);
+GRIT_GEMM_INSTANCE(GRIT_EPI_SWIGLU, true);
+GRIT_GEMM_INSTANCE(GRIT_EPI_SWIGLU_STACKED, true);
+GRIT_GEMM_INSTANCE(GRIT_EPI_ROPE, true);
+#undef GRIT_GEMM_INSTANCE
+
+// ---- the entry points: one validation, one table of epilogue rules, one dispatch.  WHICH code a wrong call gets is ABI, the order of the
+//      tests included (tests/test_gemm_abi_cpu.py holds the recorded answers); the entry points differ in what they add to one dense problem:
+struct GemmExtras {
+  const GemmGroups* groups;     // _grouped*: a_rows may be null, at most 1024 groups, tile bound on M / 256 + groups
+  const GemmRope* rope;         // _rope: K % 64 belongs to its "bad sizes", N % 128 instead of N % 16 ...
+  int S, table_rows;            //   ... and positions, or S rows of the table (S as passed: rope->S is at least 1)
+  const GemmProblem* second;    // _pair: same K; no empty problems
+};
+
+constexpr unsigned epi_bits() { return 0u; }
+template <typename... T>
+constexpr unsigned epi_bits(int e, T... rest) { return (1u << e) | epi_bits(rest...); }
+constexpr unsigned EPI_DENSE_F16 = epi_bits(GRIT_EPI_STORE, GRIT_EPI_RESIDUAL, GRIT_EPI_RESIDUAL_F32, GRIT_EPI_SWIGLU, GRIT_EPI_SWIGLU_STACKED);
+constexpr unsigned EPI_DENSE = EPI_DENSE_F16 | epi_bits(GRIT_EPI_SWIGLU_STACKED_SAVE, GRIT_EPI_SWIGLU_BWD);
+constexpr unsigned EPI_GROUPED = epi_bits(GRIT_EPI_STORE, GRIT_EPI_SWIGLU);
+constexpr unsigned EPI_GROUPED_F16 = EPI_GROUPED | epi_bits(GRIT_EPI_SWIGLU_STACKED);
+constexpr unsigned EPI_GROUPED_TRAIN = EPI_GROUPED_F16 | epi_bits(GRIT_EPI_SWIGLU_STACKED_SAVE, GRIT_EPI_SWIGLU_BWD);
+constexpr unsigned EPI_PAIR = epi_bits(GRIT_EPI_STORE, GRIT_EPI_RESIDUAL);
+
+static int check_problem(const char* fn, const GemmProblem& p, const GemmExtras& x) {
+  const GemmGroups* g = x.groups;
+  const GemmRope* rope = x.rope;
+  const bool strict = rope || x.second;           // _rope and _pair: M > 0, and ldc >= N whatever the epilogue
+  auto each = [&](auto ok) { return ok(p) && (!x.second || ok(*x.second)); };
+  GRIT_REQUIRE(each([](const GemmProblem& q) { return q.A && q.W && q.C; }) && (!g || g->counts) && (!rope || (rope->cos_tab && rope->sin_tab)),
+               GRIT_E_BADARG, "%s: null pointer", fn);
+  GRIT_REQUIRE(each([&](const GemmProblem& q) { return (strict ? q.M > 0 : q.M >= 0) && q.N > 0 && q.K > 0; }) &&
+                   (!g || (g->n_groups > 0 && g->n_groups <= 1024)) && (!rope || p.K % 64 == 0),
+               GRIT_E_BADARG, "%s: bad sizes M=%lld N=%d K=%d", fn, (long long)p.M, p.N, p.K);
+  if (rope)
+    GRIT_REQUIRE(p.N % 128 == 0 && rope->rope_cols % 128 == 0 && rope->rope_cols >= 0 && rope->rope_cols <= p.N, GRIT_E_UNSUPPORTED,
+                 "%s: N=%d and rope_cols=%d must be multiples of the head size 128", fn, p.N, rope->rope_cols);
+  GRIT_REQUIRE(p.K % 64 == 0 && each([](const GemmProblem& q) { return q.N % 16 == 0; }), GRIT_E_UNSUPPORTED,
+               "%s: K=%d must be a multiple of 64, N=%d of 16", fn, p.K, p.N);
+  GRIT_REQUIRE(each([&](const GemmProblem& q) {
+                 return q.lda % 8 == 0 && q.ldw % 8 == 0 && q.ldc % 8 == 0 && q.lda >= q.K && q.ldw >= q.K && (!strict || q.ldc >= q.N);
+               }) && (!g || g->w_stride % 8 == 0),
+               GRIT_E_BADARG, "%s: bad leading dimensions lda=%lld ldw=%lld ldc=%lld", fn, (long long)p.lda, (long long)p.ldw, (long long)p.ldc);
+  GRIT_REQUIRE(each([](const GemmProblem& q) { return aligned16(q.A) && aligned16(q.W) && aligned16(q.C); }) &&
+                   (!rope || (aligned16(rope->cos_tab) && aligned16(rope->sin_tab))),
+               GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", fn);
+  if (rope)
+    GRIT_REQUIRE((rope->positions != nullptr) ? x.table_rows > 0 : (x.S > 0 && x.table_rows >= x.S), GRIT_E_BADARG,
+                 "%s: positions or S (<= table rows) required", fn);
+  auto tiles = [&](const GemmProblem& q) { return (int64_t)(g ? q.M / BM + g->n_groups : (q.M + BM - 1) / BM) * ((q.N + BN - 1) / BN); };
+  GRIT_REQUIRE(tiles(p) + (x.second ? tiles(*x.second) : 0) < (1ll << 31), GRIT_E_UNSUPPORTED, "%s: too many tiles", fn);
+  return GRIT_OK;
+}
+
+// what an epilogue asks of ldc and of its second operand
+static int check_epilogue(const char* fn, int epilogue, const GemmProblem& p) {
+  const bool r16 = p.R && p.ldr % 8 == 0 && aligned16(p.R);         // a 16-bit second operand is there
+  switch (epilogue) {
+    case GRIT_EPI_STORE:
+      GRIT_REQUIRE(p.ldc >= p.N, GRIT_E_BADARG, "%s: ldc < N", fn);
+      break;
+    case GRIT_EPI_RESIDUAL:
+      GRIT_REQUIRE(r16 && p.ldr >= p.N && p.ldc >= p.N, GRIT_E_BADARG, "%s: RESIDUAL epilogue needs a residual with ldr >= N (and ldc >= N)", fn);
+      break;
+    case GRIT_EPI_RESIDUAL_F32:
+      GRIT_REQUIRE(p.R && p.ldr % 4 == 0 && p.ldr >= p.N && p.ldc >= p.N && p.ldc % 4 == 0 && aligned16(p.R), GRIT_E_BADARG,
+                   "%s: RESIDUAL_F32 epilogue needs an fp32 residual with ldr >= N (C and residual are fp32, ldc / ldr in floats)", fn);
+      break;
+    case GRIT_EPI_SWIGLU:
+    case GRIT_EPI_SWIGLU_STACKED:
+    case GRIT_EPI_SWIGLU_STACKED_SAVE:
+      GRIT_REQUIRE(p.N % 64 == 0 && p.ldc >= p.N / 2, GRIT_E_UNSUPPORTED, "%s: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2", fn);
+      if (epilogue == GRIT_EPI_SWIGLU_STACKED_SAVE)
+        GRIT_REQUIRE(r16 && p.ldr >= p.N, GRIT_E_BADARG, "%s: SWIGLU_STACKED_SAVE writes [gate | up] through `residual` (ldr >= N)", fn);
+      break;
+    case GRIT_EPI_SWIGLU_BWD:
+      GRIT_REQUIRE(r16 && p.ldr >= 2 * (int64_t)p.N && p.ldc >= 2 * (int64_t)p.N, GRIT_E_BADARG,
+                   "%s: SWIGLU_BWD needs the saved [gate | up] in `residual` (ldr >= 2N) and ldc >= 2N", fn);
+      break;
+  }
+  return GRIT_OK;
+}
+
+// `offered`: the epilogues of the entry point that was called (a bit per GRIT_EPI_* value)
+template <bool F16>
+static int gemm_entry(const char* fn, unsigned offered, int epilogue, GemmProblem p, void* stream, const GemmExtras& x = GemmExtras{}) {
+  if (p.M == 0 && !x.second) return GRIT_OK;      // empty batch (empty tensors have null data pointers)
+  if (const int rc = check_problem(fn, p, x)) return rc;
+  GRIT_REQUIRE(epilogue >= 0 && epilogue < 32 && ((offered >> epilogue) & 1u), GRIT_E_BADARG,
+               "%s: unknown epilogue %d, or one that is not available from this entry point", fn, epilogue);
+  if (const int rc = check_epilogue(fn, epilogue, p)) return rc;
+  if (x.second)
+    if (const int rc = check_epilogue(fn, epilogue, *x.second)) return rc;
+  const bool second_operand = epilogue == GRIT_EPI_RESIDUAL || epilogue == GRIT_EPI_RESIDUAL_F32 || epilogue == GRIT_EPI_SWIGLU_STACKED_SAVE ||
+                              epilogue == GRIT_EPI_SWIGLU_BWD;
+  if (!second_operand) { p.R = nullptr; p.ldr = 0; }
+  hipStream_t st = (hipStream_t)stream;
+  const GemmGroups grp = x.groups ? *x.groups : GemmGroups{};
+  const GemmRope rope = x.rope ? *x.rope : GemmRope{};
+  if constexpr (!F16) {                           // (the kernel refuses the training epilogues on fp16 operands at compile time)
+    if (x.second) {
+      GemmProblem p2 = *x.second;
+      if (!second_operand) { p2.R = nullptr; p2.ldr = 0; }
+      return epilogue == GRIT_EPI_STORE ? launch_gemm_pair<GRIT_EPI_STORE>(p, p2, st) : launch_gemm_pair<GRIT_EPI_RESIDUAL>(p, p2, st);
+    }
+    if (epilogue == GRIT_EPI_SWIGLU_STACKED_SAVE) return launch_gemm<GRIT_EPI_SWIGLU_STACKED_SAVE>(p, st, grp, rope);
+    if (epilogue == GRIT_EPI_SWIGLU_BWD) return launch_gemm<GRIT_EPI_SWIGLU_BWD>(p, st, grp, rope);
+  }
+  switch (epilogue) {
+    case GRIT_EPI_STORE: return launch_gemm<GRIT_EPI_STORE, F16>(p, st, grp, rope);
+    case GRIT_EPI_RESIDUAL: return launch_gemm<GRIT_EPI_RESIDUAL, F16>(p, st, grp, rope);
+    case GRIT_EPI_RESIDUAL_F32: return launch_gemm<GRIT_EPI_RESIDUAL_F32, F16>(p, st, grp, rope);
+    case GRIT_EPI_SWIGLU: return launch_gemm<GRIT_EPI_SWIGLU, F16>(p, st, grp, rope);
+    case GRIT_EPI_SWIGLU_STACKED: return launch_gemm<GRIT_EPI_SWIGLU_STACKED, F16>(p, st, grp, rope);
+    case GRIT_EPI_ROPE: return launch_gemm<GRIT_EPI_ROPE, F16>(p, st, grp, rope);
+  }
+  set_error("%s: epilogue %d has no kernel in this operand format", fn, epilogue);      // (an `offered` mask that names one)
+  return GRIT_E_BADARG;
+}
+
+template <bool F16>
+static int grouped_entry(const char* fn, unsigned offered, const void* A, const int32_t* a_rows, const void* W, void* C, const void* residual,
+                         const int32_t* group_counts, int num_groups, int64_t M_total, int N, int K, int64_t lda, int64_t ldw,
+                         int64_t w_group_stride, int64_t ldc, int64_t ldr, int epilogue, void* stream) {
+  const GemmGroups grp{group_counts, a_rows, w_group_stride, num_groups};
+  return gemm_entry<F16>(fn, offered, epilogue, GemmProblem{A, W, C, residual, M_total, N, K, lda, ldw, ldc, ldr}, stream,
+                         GemmExtras{&grp, nullptr, 0, 0, nullptr});
+}
+
+template <bool F16>
+static int rope_entry(const char* fn, const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc,
+                      const float* cos_tab, const float* sin_tab, const int32_t* positions, int S, int table_rows, int rope_cols, void* stream) {
+  const GemmRope rope{cos_tab, sin_tab, positions, S > 0 ? S : 1, rope_cols};
+  return gemm_entry<F16>(fn, 1u << GRIT_EPI_ROPE, GRIT_EPI_ROPE, GemmProblem{A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0}, stream,
+                         GemmExtras{nullptr, &rope, S, table_rows, nullptr});
 }
 
 }  // namespace grit
@@ -1219,31 +1214,37 @@ extern "C" int grit_debug_gemm_stamps(unsigned long long* host_out) {
 #endif
 extern "C" int grit_swiglu_block(void) { return 16; }
 
+// Dense: C = epilogue(A W^T); every epilogue but ROPE.
+extern "C" int grit_gemm_bf16_nt(const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw,
+                                 int64_t ldc, int epilogue, const void* residual, int64_t ldr, void* stream) {
+  return gemm_entry<false>("grit_gemm_bf16_nt", EPI_DENSE, epilogue, GemmProblem{A, W, C, residual, M, N, K, lda, ldw, ldc, ldr}, stream);
+}
+
+// ---- fp16-operand instantiations (the encoder's "f16_operands" precision policy; forward only) ----
+// Same contract as grit_gemm_bf16_nt with A, W (and C for STORE / SWIGLU) holding IEEE fp16.  STORE: C = f16(acc); SWIGLU, SWIGLU_STACKED
+// (the training engine's [gate; up] weights: pass 1 of GradCache under an fp16 policy): C = f16(silu(gate) * up) from the fp32
+// accumulators (one rounding); RESIDUAL: C (fp16) = f16(f16(acc) + residual) with an fp16 residual (the fp16 residual stream of the
+// "f16_stream" policy); RESIDUAL_F32: C (fp32) = residual (fp32) + acc.  A result beyond the fp16 range sets the device's overflow flag
+// (grit_f16_overflow_flag).
+extern "C" int grit_gemm_f16_nt(const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw,
+                                int64_t ldc, int epilogue, const void* residual, int64_t ldr, void* stream) {
+  return gemm_entry<true>("grit_gemm_f16_nt", EPI_DENSE_F16, epilogue, GemmProblem{A, W, C, residual, M, N, K, lda, ldw, ldc, ldr}, stream);
+}
+
+// Grouped (GemmGroups above): STORE, SWIGLU (interleaved weights); fp16 operands (Mixtral's expert MLP under the "f16_operands" policy: A
+// gathered through a_rows, W [E,N,K] and C in fp16, one rounding of the fp32 accumulator) also SWIGLU_STACKED.
 extern "C" int grit_gemm_bf16_nt_grouped(const void* A, const int32_t* a_rows, const void* W, void* C, const int32_t* group_counts,
                                          int num_groups, int64_t M_total, int N, int K, int64_t lda, int64_t ldw, int64_t w_group_stride,
                                          int64_t ldc, int epilogue, void* stream) {
-  if (M_total == 0) return GRIT_OK;
-  GRIT_REQUIRE(A && W && C && group_counts, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped: null pointer");
-  GRIT_REQUIRE(M_total >= 0 && N > 0 && K > 0 && num_groups > 0 && num_groups <= 1024, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped: bad sizes");
-  GRIT_REQUIRE(K % 64 == 0 && N % 16 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_grouped: K=%d must be a multiple of 64, N=%d of 16", K, N);
-  GRIT_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && w_group_stride % 8 == 0 && lda >= K && ldw >= K, GRIT_E_BADARG,
-               "grit_gemm_bf16_nt_grouped: bad leading dimensions");
-  GRIT_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C), GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)(M_total / BM + num_groups) * ((N + BN - 1) / BN) < (1ll << 31), GRIT_E_UNSUPPORTED,
-               "grit_gemm_bf16_nt_grouped: too many tiles");
-  const GemmGroups grp{group_counts, a_rows, w_group_stride, num_groups};
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case GRIT_EPI_STORE:
-      GRIT_REQUIRE(ldc >= N, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped: ldc < N");
-      return launch_gemm<GRIT_EPI_STORE>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    case GRIT_EPI_SWIGLU:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_grouped: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    default:
-      GRIT_REQUIRE(false, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped: epilogue %d not available (STORE, SWIGLU)", epilogue);
-  }
-  return GRIT_OK;
+  return grouped_entry<false>("grit_gemm_bf16_nt_grouped", EPI_GROUPED, A, a_rows, W, C, nullptr, group_counts, num_groups, M_total, N, K, lda, ldw,
+                              w_group_stride, ldc, 0, epilogue, stream);
+}
+
+extern "C" int grit_gemm_f16_nt_grouped(const void* A, const int32_t* a_rows, const void* W, void* C, const int32_t* group_counts,
+                                        int num_groups, int64_t M_total, int N, int K, int64_t lda, int64_t ldw, int64_t w_group_stride,
+                                        int64_t ldc, int epilogue, void* stream) {
+  return grouped_entry<true>("grit_gemm_f16_nt_grouped", EPI_GROUPED_F16, A, a_rows, W, C, nullptr, group_counts, num_groups, M_total, N, K, lda,
+                             ldw, w_group_stride, ldc, 0, epilogue, stream);
 }
 
 // Grouped launch with the training epilogues (Mixtral's expert MLP, forward with saved pre-activations and backward):
@@ -1252,59 +1253,22 @@ extern "C" int grit_gemm_bf16_nt_grouped(const void* A, const int32_t* a_rows, c
 extern "C" int grit_gemm_bf16_nt_grouped_epi(const void* A, const int32_t* a_rows, const void* W, void* C, const void* residual,
                                              const int32_t* group_counts, int num_groups, int64_t M_total, int N, int K, int64_t lda,
                                              int64_t ldw, int64_t w_group_stride, int64_t ldc, int64_t ldr, int epilogue, void* stream) {
-  if (M_total == 0) return GRIT_OK;
-  GRIT_REQUIRE(A && W && C && group_counts, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped_epi: null pointer");
-  GRIT_REQUIRE(M_total >= 0 && N > 0 && K > 0 && num_groups > 0 && num_groups <= 1024, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped_epi: bad sizes");
-  GRIT_REQUIRE(K % 64 == 0 && N % 16 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_grouped_epi: K=%d must be a multiple of 64, N=%d of 16", K, N);
-  GRIT_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && w_group_stride % 8 == 0 && lda >= K && ldw >= K, GRIT_E_BADARG,
-               "grit_gemm_bf16_nt_grouped_epi: bad leading dimensions");
-  GRIT_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C), GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped_epi: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)(M_total / BM + num_groups) * ((N + BN - 1) / BN) < (1ll << 31), GRIT_E_UNSUPPORTED,
-               "grit_gemm_bf16_nt_grouped_epi: too many tiles");
-  const GemmGroups grp{group_counts, a_rows, w_group_stride, num_groups};
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case GRIT_EPI_STORE:
-      GRIT_REQUIRE(ldc >= N, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped_epi: ldc < N");
-      return launch_gemm<GRIT_EPI_STORE>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    case GRIT_EPI_SWIGLU:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_grouped_epi: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    case GRIT_EPI_SWIGLU_STACKED:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_grouped_epi: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU_STACKED>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    case GRIT_EPI_SWIGLU_STACKED_SAVE:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_grouped_epi: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      GRIT_REQUIRE(residual && ldr % 8 == 0 && ldr >= N && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_bf16_nt_grouped_epi: SWIGLU_STACKED_SAVE writes [gate | up] through `residual` (ldr >= N)");
-      return launch_gemm<GRIT_EPI_SWIGLU_STACKED_SAVE>(A, W, C, residual, M_total, N, K, lda, ldw, ldc, ldr, st, grp);
-    case GRIT_EPI_SWIGLU_BWD:
-      GRIT_REQUIRE(residual && ldr % 8 == 0 && ldr >= 2 * (int64_t)N && ldc >= 2 * (int64_t)N && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_bf16_nt_grouped_epi: SWIGLU_BWD needs the saved [gate | up] in `residual` (ldr >= 2N) and ldc >= 2N");
-      return launch_gemm<GRIT_EPI_SWIGLU_BWD>(A, W, C, residual, M_total, N, K, lda, ldw, ldc, ldr, st, grp);
-    default:
-      GRIT_REQUIRE(false, GRIT_E_BADARG, "grit_gemm_bf16_nt_grouped_epi: epilogue %d not available", epilogue);
-  }
-  return GRIT_OK;
+  return grouped_entry<false>("grit_gemm_bf16_nt_grouped_epi", EPI_GROUPED_TRAIN, A, a_rows, W, C, residual, group_counts, num_groups, M_total, N, K,
+                              lda, ldw, w_group_stride, ldc, ldr, epilogue, stream);
 }
 
+// STORE with the rotary embedding (GemmRope above).  fp16 operands: the rotation runs on the fp32 accumulators with the UNROUNDED fp32
+// tables the caller passes, q | k | v are rounded once, to fp16.
 extern "C" int grit_gemm_bf16_nt_rope(const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc,
                                       const float* cos_tab, const float* sin_tab, const int32_t* positions, int S, int table_rows,
                                       int rope_cols, void* stream) {
-  if (M == 0) return GRIT_OK;
-  GRIT_REQUIRE(A && W && C && cos_tab && sin_tab, GRIT_E_BADARG, "grit_gemm_bf16_nt_rope: null pointer");
-  GRIT_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0, GRIT_E_BADARG, "grit_gemm_bf16_nt_rope: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-  GRIT_REQUIRE(N % 128 == 0 && rope_cols % 128 == 0 && rope_cols >= 0 && rope_cols <= N, GRIT_E_UNSUPPORTED,
-               "grit_gemm_bf16_nt_rope: N=%d and rope_cols=%d must be multiples of the head size 128", N, rope_cols);
-  GRIT_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && lda >= K && ldw >= K && ldc >= N, GRIT_E_BADARG,
-               "grit_gemm_bf16_nt_rope: bad leading dimensions");
-  GRIT_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C) && aligned16(cos_tab) && aligned16(sin_tab), GRIT_E_BADARG,
-               "grit_gemm_bf16_nt_rope: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((positions != nullptr) ? table_rows > 0 : (S > 0 && table_rows >= S), GRIT_E_BADARG,
-               "grit_gemm_bf16_nt_rope: positions or S (<= table rows) required");
-  GRIT_REQUIRE((int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN) < (1ll << 31), GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_rope: too many tiles");
-  const GemmRope rope{cos_tab, sin_tab, positions, S > 0 ? S : 1, rope_cols};
-  return launch_gemm<GRIT_EPI_ROPE>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, (hipStream_t)stream, GemmGroups{nullptr, nullptr, 0, 0}, rope);
+  return rope_entry<false>("grit_gemm_bf16_nt_rope", A, W, C, M, N, K, lda, ldw, ldc, cos_tab, sin_tab, positions, S, table_rows, rope_cols, stream);
+}
+
+extern "C" int grit_gemm_f16_nt_rope(const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc,
+                                     const float* cos_tab, const float* sin_tab, const int32_t* positions, int S, int table_rows,
+                                     int rope_cols, void* stream) {
+  return rope_entry<true>("grit_gemm_f16_nt_rope", A, W, C, M, N, K, lda, ldw, ldc, cos_tab, sin_tab, positions, S, table_rows, rope_cols, stream);
 }
 
 // Two dense GEMMs with the same K and epilogue (STORE or RESIDUAL) in ONE launch: the weight-gradient GEMMs of a layer whose tile counts
@@ -1312,166 +1276,7 @@ extern "C" int grit_gemm_bf16_nt_rope(const void* A, const void* W, void* C, int
 extern "C" int grit_gemm_bf16_nt_pair(const void* A1, const void* W1, void* C1, const void* R1, int64_t M1, int N1, int64_t lda1, int64_t ldw1,
                                       int64_t ldc1, int64_t ldr1, const void* A2, const void* W2, void* C2, const void* R2, int64_t M2, int N2,
                                       int64_t lda2, int64_t ldw2, int64_t ldc2, int64_t ldr2, int K, int epilogue, void* stream) {
-  GRIT_REQUIRE(A1 && W1 && C1 && A2 && W2 && C2, GRIT_E_BADARG, "grit_gemm_bf16_nt_pair: null pointer");
-  GRIT_REQUIRE(M1 > 0 && N1 > 0 && M2 > 0 && N2 > 0 && K > 0, GRIT_E_BADARG, "grit_gemm_bf16_nt_pair: bad sizes");
-  GRIT_REQUIRE(K % 64 == 0 && N1 % 16 == 0 && N2 % 16 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_pair: K must be a multiple of 64, N of 16");
-  GRIT_REQUIRE(lda1 % 8 == 0 && ldw1 % 8 == 0 && ldc1 % 8 == 0 && lda2 % 8 == 0 && ldw2 % 8 == 0 && ldc2 % 8 == 0 && lda1 >= K && ldw1 >= K &&
-                   lda2 >= K && ldw2 >= K && ldc1 >= N1 && ldc2 >= N2,
-               GRIT_E_BADARG, "grit_gemm_bf16_nt_pair: bad leading dimensions");
-  GRIT_REQUIRE(aligned16(A1) && aligned16(W1) && aligned16(C1) && aligned16(A2) && aligned16(W2) && aligned16(C2), GRIT_E_BADARG,
-               "grit_gemm_bf16_nt_pair: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)((M1 + BM - 1) / BM) * ((N1 + BN - 1) / BN) + (int64_t)((M2 + BM - 1) / BM) * ((N2 + BN - 1) / BN) < (1ll << 31),
-               GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt_pair: too many tiles");
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case GRIT_EPI_STORE:
-      return launch_gemm_pair<GRIT_EPI_STORE>(A1, W1, C1, nullptr, M1, N1, lda1, ldw1, ldc1, 0, A2, W2, C2, nullptr, M2, N2, lda2, ldw2, ldc2, 0, K, st);
-    case GRIT_EPI_RESIDUAL:
-      GRIT_REQUIRE(R1 && R2 && ldr1 % 8 == 0 && ldr2 % 8 == 0 && ldr1 >= N1 && ldr2 >= N2 && aligned16(R1) && aligned16(R2), GRIT_E_BADARG,
-                   "grit_gemm_bf16_nt_pair: RESIDUAL epilogue needs both residuals (ldr >= N)");
-      return launch_gemm_pair<GRIT_EPI_RESIDUAL>(A1, W1, C1, R1, M1, N1, lda1, ldw1, ldc1, ldr1, A2, W2, C2, R2, M2, N2, lda2, ldw2, ldc2, ldr2, K, st);
-    default:
-      GRIT_REQUIRE(false, GRIT_E_BADARG, "grit_gemm_bf16_nt_pair: epilogue %d not available (STORE, RESIDUAL)", epilogue);
-  }
-  return GRIT_OK;
-}
-
-extern "C" int grit_gemm_bf16_nt(const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw,
-                                 int64_t ldc, int epilogue, const void* residual, int64_t ldr, void* stream) {
-  if (M == 0) return GRIT_OK;  // empty batch (empty tensors have null data pointers)
-  GRIT_REQUIRE(A && W && C, GRIT_E_BADARG, "grit_gemm_bf16_nt: null pointer");
-  GRIT_REQUIRE(M >= 0 && N > 0 && K > 0, GRIT_E_BADARG, "grit_gemm_bf16_nt: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-  GRIT_REQUIRE(K % 64 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt: K=%d must be a multiple of 64", K);
-  GRIT_REQUIRE(N % 16 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt: N=%d must be a multiple of 16", N);
-  GRIT_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && lda >= K && ldw >= K, GRIT_E_BADARG,
-               "grit_gemm_bf16_nt: bad leading dimensions lda=%lld ldw=%lld ldc=%lld", (long long)lda, (long long)ldw, (long long)ldc);
-  GRIT_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C), GRIT_E_BADARG, "grit_gemm_bf16_nt: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN) < (1ll << 31), GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt: too many tiles");
-  if (M == 0) return GRIT_OK;
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case GRIT_EPI_STORE:
-      GRIT_REQUIRE(ldc >= N, GRIT_E_BADARG, "grit_gemm_bf16_nt: ldc < N");
-      return launch_gemm<GRIT_EPI_STORE>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, st);
-    case GRIT_EPI_RESIDUAL:
-      GRIT_REQUIRE(residual && ldr % 8 == 0 && ldr >= N && ldc >= N && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_bf16_nt: RESIDUAL epilogue needs residual with ldr >= N");
-      return launch_gemm<GRIT_EPI_RESIDUAL>(A, W, C, residual, M, N, K, lda, ldw, ldc, ldr, st);
-    case GRIT_EPI_RESIDUAL_F32:
-      GRIT_REQUIRE(residual && ldr % 4 == 0 && ldr >= N && ldc >= N && ldc % 4 == 0 && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_bf16_nt: RESIDUAL_F32 epilogue needs an fp32 residual with ldr >= N (C and residual are fp32, ldc / ldr in floats)");
-      return launch_gemm<GRIT_EPI_RESIDUAL_F32>(A, W, C, residual, M, N, K, lda, ldw, ldc, ldr, st);
-    case GRIT_EPI_SWIGLU:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, st);
-    case GRIT_EPI_SWIGLU_STACKED:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU_STACKED>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, st);
-    case GRIT_EPI_SWIGLU_STACKED_SAVE:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_bf16_nt: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      GRIT_REQUIRE(residual && ldr % 8 == 0 && ldr >= N && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_bf16_nt: SWIGLU_STACKED_SAVE writes [gate | up] through `residual` (ldr >= N)");
-      return launch_gemm<GRIT_EPI_SWIGLU_STACKED_SAVE>(A, W, C, residual, M, N, K, lda, ldw, ldc, ldr, st);
-    case GRIT_EPI_SWIGLU_BWD:
-      GRIT_REQUIRE(residual && ldr % 8 == 0 && ldr >= 2 * (int64_t)N && ldc >= 2 * (int64_t)N && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_bf16_nt: SWIGLU_BWD needs the saved [gate | up] in `residual` (ldr >= 2N) and ldc >= 2N");
-      return launch_gemm<GRIT_EPI_SWIGLU_BWD>(A, W, C, residual, M, N, K, lda, ldw, ldc, ldr, st);
-    default:
-      GRIT_REQUIRE(false, GRIT_E_BADARG, "grit_gemm_bf16_nt: unknown epilogue %d", epilogue);
-  }
-  return GRIT_OK;
-}
-
-// ---- fp16-operand instantiations (the encoder's "f16_operands" precision policy; forward only, dense) ----
-// Same contract as grit_gemm_bf16_nt with A, W (and C for STORE / SWIGLU) holding IEEE fp16.  STORE: C = f16(acc); SWIGLU: C =
-// f16(silu(gate) * up) from the fp32 accumulators (one rounding; interleaved weight rows, grit_swiglu_block()); RESIDUAL: C (fp16) =
-// f16(f16(acc) + residual) with an fp16 residual (the fp16 residual stream of the "f16_stream" policy); RESIDUAL_F32: C (fp32)
-// = residual (fp32) + acc.  A result beyond the fp16 range sets the device's overflow flag (grit_f16_overflow_flag).
-extern "C" int grit_gemm_f16_nt(const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw,
-                                int64_t ldc, int epilogue, const void* residual, int64_t ldr, void* stream) {
-  if (M == 0) return GRIT_OK;
-  GRIT_REQUIRE(A && W && C, GRIT_E_BADARG, "grit_gemm_f16_nt: null pointer");
-  GRIT_REQUIRE(M >= 0 && N > 0 && K > 0, GRIT_E_BADARG, "grit_gemm_f16_nt: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-  GRIT_REQUIRE(K % 64 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt: K=%d must be a multiple of 64", K);
-  GRIT_REQUIRE(N % 16 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt: N=%d must be a multiple of 16", N);
-  GRIT_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && lda >= K && ldw >= K, GRIT_E_BADARG,
-               "grit_gemm_f16_nt: bad leading dimensions lda=%lld ldw=%lld ldc=%lld", (long long)lda, (long long)ldw, (long long)ldc);
-  GRIT_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C), GRIT_E_BADARG, "grit_gemm_f16_nt: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN) < (1ll << 31), GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt: too many tiles");
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case GRIT_EPI_STORE:
-      GRIT_REQUIRE(ldc >= N, GRIT_E_BADARG, "grit_gemm_f16_nt: ldc < N");
-      return launch_gemm<GRIT_EPI_STORE, true>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, st);
-    case GRIT_EPI_RESIDUAL:
-      GRIT_REQUIRE(residual && ldr % 8 == 0 && ldr >= N && ldc >= N && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_f16_nt: RESIDUAL epilogue needs an fp16 residual with ldr >= N");
-      return launch_gemm<GRIT_EPI_RESIDUAL, true>(A, W, C, residual, M, N, K, lda, ldw, ldc, ldr, st);
-    case GRIT_EPI_RESIDUAL_F32:
-      GRIT_REQUIRE(residual && ldr % 4 == 0 && ldr >= N && ldc >= N && ldc % 4 == 0 && aligned16(residual), GRIT_E_BADARG,
-                   "grit_gemm_f16_nt: RESIDUAL_F32 epilogue needs an fp32 residual with ldr >= N (C and residual are fp32, ldc / ldr in floats)");
-      return launch_gemm<GRIT_EPI_RESIDUAL_F32, true>(A, W, C, residual, M, N, K, lda, ldw, ldc, ldr, st);
-    case GRIT_EPI_SWIGLU:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU, true>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, st);
-    case GRIT_EPI_SWIGLU_STACKED:     // the training engine's [gate; up] weights (pass 1 of GradCache under an fp16 policy)
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU_STACKED, true>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, st);
-    default:
-      GRIT_REQUIRE(false, GRIT_E_BADARG, "grit_gemm_f16_nt: epilogue %d not available (STORE, SWIGLU, SWIGLU_STACKED, RESIDUAL, RESIDUAL_F32)", epilogue);
-  }
-  return GRIT_OK;
-}
-
-// grit_gemm_bf16_nt_grouped on fp16 operands (Mixtral's expert MLP under the "f16_operands" policy): A (gathered through a_rows), W
-// [E,N,K] and C in fp16, one rounding of the fp32 accumulator (SWIGLU / SWIGLU_STACKED: of silu(gate) * up evaluated in fp32).
-extern "C" int grit_gemm_f16_nt_grouped(const void* A, const int32_t* a_rows, const void* W, void* C, const int32_t* group_counts,
-                                        int num_groups, int64_t M_total, int N, int K, int64_t lda, int64_t ldw, int64_t w_group_stride,
-                                        int64_t ldc, int epilogue, void* stream) {
-  if (M_total == 0) return GRIT_OK;
-  GRIT_REQUIRE(A && W && C && group_counts, GRIT_E_BADARG, "grit_gemm_f16_nt_grouped: null pointer");
-  GRIT_REQUIRE(M_total >= 0 && N > 0 && K > 0 && num_groups > 0 && num_groups <= 1024, GRIT_E_BADARG, "grit_gemm_f16_nt_grouped: bad sizes");
-  GRIT_REQUIRE(K % 64 == 0 && N % 16 == 0, GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt_grouped: K=%d must be a multiple of 64, N=%d of 16", K, N);
-  GRIT_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && w_group_stride % 8 == 0 && lda >= K && ldw >= K, GRIT_E_BADARG,
-               "grit_gemm_f16_nt_grouped: bad leading dimensions");
-  GRIT_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C), GRIT_E_BADARG, "grit_gemm_f16_nt_grouped: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)(M_total / BM + num_groups) * ((N + BN - 1) / BN) < (1ll << 31), GRIT_E_UNSUPPORTED,
-               "grit_gemm_f16_nt_grouped: too many tiles");
-  const GemmGroups grp{group_counts, a_rows, w_group_stride, num_groups};
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case GRIT_EPI_STORE:
-      GRIT_REQUIRE(ldc >= N, GRIT_E_BADARG, "grit_gemm_f16_nt_grouped: ldc < N");
-      return launch_gemm<GRIT_EPI_STORE, true>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    case GRIT_EPI_SWIGLU:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt_grouped: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU, true>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    case GRIT_EPI_SWIGLU_STACKED:
-      GRIT_REQUIRE(N % 64 == 0 && ldc >= N / 2, GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt_grouped: SWIGLU epilogue needs N %% 64 == 0 and ldc >= N/2");
-      return launch_gemm<GRIT_EPI_SWIGLU_STACKED, true>(A, W, C, nullptr, M_total, N, K, lda, ldw, ldc, 0, st, grp);
-    default:
-      GRIT_REQUIRE(false, GRIT_E_BADARG, "grit_gemm_f16_nt_grouped: epilogue %d not available (STORE, SWIGLU, SWIGLU_STACKED)", epilogue);
-  }
-  return GRIT_OK;
-}
-
-// grit_gemm_bf16_nt_rope on fp16 operands: the rotation runs on the fp32 accumulators with the UNROUNDED fp32 tables the caller passes,
-// q | k | v are rounded once, to fp16.
-extern "C" int grit_gemm_f16_nt_rope(const void* A, const void* W, void* C, int64_t M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc,
-                                     const float* cos_tab, const float* sin_tab, const int32_t* positions, int S, int table_rows,
-                                     int rope_cols, void* stream) {
-  if (M == 0) return GRIT_OK;
-  GRIT_REQUIRE(A && W && C && cos_tab && sin_tab, GRIT_E_BADARG, "grit_gemm_f16_nt_rope: null pointer");
-  GRIT_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0, GRIT_E_BADARG, "grit_gemm_f16_nt_rope: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-  GRIT_REQUIRE(N % 128 == 0 && rope_cols % 128 == 0 && rope_cols >= 0 && rope_cols <= N, GRIT_E_UNSUPPORTED,
-               "grit_gemm_f16_nt_rope: N=%d and rope_cols=%d must be multiples of the head size 128", N, rope_cols);
-  GRIT_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && lda >= K && ldw >= K && ldc >= N, GRIT_E_BADARG,
-               "grit_gemm_f16_nt_rope: bad leading dimensions");
-  GRIT_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C) && aligned16(cos_tab) && aligned16(sin_tab), GRIT_E_BADARG,
-               "grit_gemm_f16_nt_rope: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((positions != nullptr) ? table_rows > 0 : (S > 0 && table_rows >= S), GRIT_E_BADARG,
-               "grit_gemm_f16_nt_rope: positions or S (<= table rows) required");
-  GRIT_REQUIRE((int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN) < (1ll << 31), GRIT_E_UNSUPPORTED, "grit_gemm_f16_nt_rope: too many tiles");
-  const GemmRope rope{cos_tab, sin_tab, positions, S > 0 ? S : 1, rope_cols};
-  return launch_gemm<GRIT_EPI_ROPE, true>(A, W, C, nullptr, M, N, K, lda, ldw, ldc, 0, (hipStream_t)stream, GemmGroups{nullptr, nullptr, 0, 0}, rope);
+  const GemmProblem second{A2, W2, C2, R2, M2, N2, K, lda2, ldw2, ldc2, ldr2};
+  return gemm_entry<false>("grit_gemm_bf16_nt_pair", EPI_PAIR, epilogue, GemmProblem{A1, W1, C1, R1, M1, N1, K, lda1, ldw1, ldc1, ldr1}, stream,
+                           GemmExtras{nullptr, nullptr, 0, 0, &second});
 }

@@ -50,7 +50,7 @@ def test_mfma_kernels_do_not_spill(src, needle, count):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 @pytest.mark.parametrize("inst,mfma", [("Li1ELb1ELb0E", "v_mfma_f32_16x16x32_bf16"), ("Li7ELb1ELb1E", "v_mfma_f32_16x16x32_f16")])
 def test_gemm_k_loop_hands_the_matrix_pipe_over_one_product_early(inst, mfma):
-    """ISA-level guard of the round-4 hand-over (csrc/gemm_bf16.hip, GRIT_GEMM_BAR_EARLY = 1): in the persistent RESIDUAL instantiation
+    """ISA-level guard of the round-4 hand-over (csrc/gemm_bf16.hip, BAR_AT = 14): in the persistent RESIDUAL instantiation
     every MFMA segment of the K loop is 15 products, s_barrier, ONE product, s_setprio 0 -- hipcc must neither move products across the
     barrier nor merge segments (a barrier behind the last product costs 1-2.6 % per shape, two products early 6-8 %:
     profiles/r04_gemm_barrier_ab.log) -- and no s_waitcnt vmcnt(0) (a drain of the LDS-DMA queue) sits between two segments of a K-tile."""
