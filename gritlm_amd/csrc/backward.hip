@@ -1,8 +1,6 @@
 // HBM-bound backward pieces of the contrastive training step (autograd of the ops in elementwise.hip /
 // the MLP activation): RMSNorm backward (+ fused residual-gradient add), SwiGLU forward/backward on the
 // concatenated [gate | up] layout used by the training engine, embedding scatter-add, small helpers.
-#include <atomic>
-
 #include "common.h"
 
 namespace grit {
@@ -259,27 +257,9 @@ __global__ void __launch_bounds__(256) accum_bf16_from_f32_k(uint16_t* __restric
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) acc[i] = (uint16_t)f2bf(bf2f(acc[i]) + x[i]);
 }
 
-static inline int grid_for(int64_t items) {
-  int64_t g = (items + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
 }  // namespace grit
 
 using namespace grit;
-
-// A dynamic-LDS opt-in is a PER-DEVICE function attribute: set once per (kernel, device), from whichever thread gets there first
-// (autograd worker threads call into the backward entry points concurrently).
-template <typename KernelT>
-static void lds_optin_once(KernelT kernel, std::atomic<uint64_t>& done, int bytes) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done.fetch_or(bit, std::memory_order_release);
-  }
-}
 
 extern "C" {
 
@@ -297,8 +277,6 @@ int grit_rmsnorm_bwd(const void* dy, const void* x, const void* w, const void* d
   GRIT_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(w) && aligned16(dx) && (dres == nullptr || aligned16(dres)), GRIT_E_BADARG,
                "grit_rmsnorm_bwd: pointers must be 16-byte aligned");
   const int nblk = (int)grit_rmsnorm_bwd_workspace_rows(T);
-  static std::atomic<uint64_t> optin{0};
-  lds_optin_once(rmsnorm_bwd_k, optin, 128 * 1024);
   hipStream_t st = (hipStream_t)stream;
 #define GRIT_RMSBWD_REG(NCH_)                                                                                                   \
   hipLaunchKernelGGL(rmsnorm_bwd_reg_k<NCH_>, dim3(nblk), dim3(256), 0, st, (const uint4*)dy, (const uint4*)x, (const uint4*)w,      \
@@ -307,9 +285,11 @@ int grit_rmsnorm_bwd(const void* dy, const void* x, const void* w, const void* d
   else if (H == 1024) GRIT_RMSBWD_REG(2);
   else if (H == 2048) GRIT_RMSBWD_REG(4);
   else if (H == 4096) GRIT_RMSBWD_REG(8);
-  else
+  else {
+    lds_optin_once<rmsnorm_bwd_k>(128 * 1024);
     hipLaunchKernelGGL(rmsnorm_bwd_k, dim3(nblk), dim3(256), (size_t)H * 4, st, (const uint4*)dy, (const uint4*)x, (const uint4*)w,
                        (const uint4*)dres, (uint4*)dx, dw_partial, T, H, eps);
+  }
   GRIT_CHECK_LAUNCH("grit_rmsnorm_bwd");
   hipLaunchKernelGGL(rmsnorm_dw_reduce_k, dim3((H + 63) / 64), dim3(256), 0, st, (const float*)dw_partial, dw, nblk, H);
   GRIT_CHECK_LAUNCH("grit_rmsnorm_bwd: reduce");

@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+#include <type_traits>
+
 #include "../../include/gritlm_hip.h"
 
 namespace grit {
@@ -32,6 +35,34 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// host: blocks of `threads` over `items` work items, at most 8 blocks per CU (2048); the kernels grid-stride the rest
+static inline int grid_for(int64_t items, int threads = 256) {
+  const int64_t g = (items + threads - 1) / threads;
+  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+}
+
+// A dynamic-LDS opt-in is a PER-DEVICE function attribute: set once per (kernel, device), from whichever thread gets there first
+// (autograd worker threads call into the backward entry points concurrently).
+template <auto Kernel>
+static void lds_optin_once(int bytes) {
+  static std::atomic<uint64_t> done{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t bit = 1ull << (dev & 63);
+  if (!(done.load(std::memory_order_acquire) & bit)) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done.fetch_or(bit, std::memory_order_release);
+  }
+}
+
+// host: the run-time expert count (validated by the caller: 4, 8 or 16) as a compile-time one -- f(std::integral_constant<int, E>)
+template <typename F>
+static inline void with_experts(int E, F&& f) {
+  if (E == 4) f(std::integral_constant<int, 4>{});
+  else if (E == 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
 
 // ---- bf16 <-> f32 (bit tricks; RNE like torch's .to(bfloat16)) ----
 __device__ __forceinline__ float bf2f(uint16_t u) { return __uint_as_float(((uint32_t)u) << 16); }

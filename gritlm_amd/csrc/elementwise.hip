@@ -18,21 +18,10 @@ void set_error(const char* fmt, ...) {
 
 // ---------------------------------------------------------------- embedding gather
 // scripts/modeling_mistral_gritlm.py:994  inputs_embeds = self.embed_tokens(input_ids)
+// F32: the fp32 residual stream (opt-in, DESIGN "precision policy"): the same gather, rows widened to fp32 (exact)
+template <bool F32>
 __global__ void __launch_bounds__(256) embed_gather_k(const uint4* __restrict__ table, const int64_t* __restrict__ ids,
-                                                      uint4* __restrict__ out, int64_t T, int HC, int64_t V) {
-  const int64_t total = T * HC;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t t = i / HC;
-    const int c = (int)(i - t * HC);
-    int64_t id = ids[t];
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-    out[i] = table[id * HC + c];
-  }
-}
-
-// fp32 residual stream (opt-in, DESIGN "precision policy"): the same gather, rows widened to fp32 (exact)
-__global__ void __launch_bounds__(256) embed_gather_f32_k(const uint4* __restrict__ table, const int64_t* __restrict__ ids,
-                                                          float4* __restrict__ out, int64_t T, int HC, int64_t V) {
+                                                      std::conditional_t<F32, float4, uint4>* __restrict__ out, int64_t T, int HC, int64_t V) {
   const int64_t total = T * HC;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t t = i / HC;
@@ -40,190 +29,99 @@ __global__ void __launch_bounds__(256) embed_gather_f32_k(const uint4* __restric
     int64_t id = ids[t];
     id = id < 0 ? 0 : (id >= V ? V - 1 : id);
     const uint4 v = table[id * HC + c];
-    out[2 * i] = make_float4(bflo(v.x), bfhi(v.x), bflo(v.y), bfhi(v.y));
-    out[2 * i + 1] = make_float4(bflo(v.z), bfhi(v.z), bflo(v.w), bfhi(v.w));
+    if constexpr (F32) {
+      out[2 * i] = make_float4(bflo(v.x), bfhi(v.x), bflo(v.y), bfhi(v.y));
+      out[2 * i + 1] = make_float4(bflo(v.z), bfhi(v.z), bflo(v.w), bfhi(v.w));
+    } else {
+      out[i] = v;
+    }
   }
 }
 
 // ---------------------------------------------------------------- RMSNorm forward
-// scripts/modeling_mistral_gritlm.py:84-89.  One wave per row, row held in registers when H = NCH*512.
-__device__ __forceinline__ float sumsq8(const uint4& v) {
-  float s = 0.f, a;
-  a = bflo(v.x); s += a * a; a = bfhi(v.x); s += a * a;
-  a = bflo(v.y); s += a * a; a = bfhi(v.y); s += a * a;
-  a = bflo(v.z); s += a * a; a = bfhi(v.z); s += a * a;
-  a = bflo(v.w); s += a * a; a = bfhi(v.w); s += a * a;
-  return s;
+// scripts/modeling_mistral_gritlm.py:84-89.  One kernel for every precision policy: x [T,H] in bf16 (the reference's stream), fp32 (the
+// "f16_operands" policy's residual stream) or fp16 (the "f16_stream" policy); w bf16; y bf16, or fp16 (OUT_F16: the operand of the next
+// GEMM; a value beyond the fp16 range sets the overflow flag word `ovf`).  One wave per row; a lane owns the 16-byte piece c*64 + lane of
+// x (8 elements, fp32: 4), so every load instruction covers 1 KiB contiguous; the row is held in registers when it is NCH * 64 pieces.
+enum class RowFmt { BF16, F16, F32 };
+template <RowFmt IN> using row_piece_t = std::conditional_t<IN == RowFmt::F32, float4, uint4>;   // 16 bytes of x
+template <RowFmt IN> using out_piece_t = std::conditional_t<IN == RowFmt::F32, uint2, uint4>;    // the same elements of w and y
+
+// sum of squares of one piece: a chain over its elements (the caller adds it to the running sum)
+template <RowFmt IN>
+__device__ __forceinline__ float sumsq(const row_piece_t<IN>& v) {
+  if constexpr (IN == RowFmt::F32) {
+    return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+  } else {
+    constexpr bool H16 = IN == RowFmt::F16;
+    float s = 0.f, a;
+    a = lo16_op<H16>(v.x); s += a * a; a = hi16_op<H16>(v.x); s += a * a;
+    a = lo16_op<H16>(v.y); s += a * a; a = hi16_op<H16>(v.y); s += a * a;
+    a = lo16_op<H16>(v.z); s += a * a; a = hi16_op<H16>(v.z); s += a * a;
+    a = lo16_op<H16>(v.w); s += a * a; a = hi16_op<H16>(v.w); s += a * a;
+    return s;
+  }
 }
-__device__ __forceinline__ uint32_t norm2(uint32_t x, uint32_t w, float rs) {
-  // bf16(w * bf16(x*rs)) for both halves: the reference rounds after the normalise and after the weight
-  const float lo = bflo(w) * round_bf(bflo(x) * rs);
-  const float hi = bfhi(w) * round_bf(bfhi(x) * rs);
-  return pack2bf(lo, hi);
+template <RowFmt IN, bool OUT_F16>
+__device__ __forceinline__ uint32_t norm2(float x0, float x1, uint32_t w, float rs) {
+  if constexpr (IN == RowFmt::BF16) {
+    // bf16(w * bf16(x*rs)) for both halves: the reference rounds after the normalise and after the weight
+    return pack2bf(bflo(w) * round_bf(x0 * rs), bfhi(w) * round_bf(x1 * rs));
+  } else {
+    // fp32 / fp16 stream: w * (x * rs) in fp32 with ONE rounding (what the reference computes when it runs in fp32)
+    return pack2_op<OUT_F16>(bflo(w) * (x0 * rs), bfhi(w) * (x1 * rs));
+  }
 }
-__device__ __forceinline__ uint4 norm8(const uint4& x, const uint4& w, float rs) {
-  uint4 o;
-  o.x = norm2(x.x, w.x, rs); o.y = norm2(x.y, w.y, rs); o.z = norm2(x.z, w.z, rs); o.w = norm2(x.w, w.w, rs);
+template <RowFmt IN, bool OUT_F16>
+__device__ __forceinline__ out_piece_t<IN> norm_piece(const row_piece_t<IN>& x, const out_piece_t<IN>& w, float rs, uint32_t& bad) {
+  out_piece_t<IN> o;
+  if constexpr (IN == RowFmt::F32) {
+    o.x = norm2<IN, OUT_F16>(x.x, x.y, w.x, rs); o.y = norm2<IN, OUT_F16>(x.z, x.w, w.y, rs);
+    if constexpr (OUT_F16) bad |= h2_nonfinite(o.x) | h2_nonfinite(o.y);
+  } else {
+    constexpr bool H16 = IN == RowFmt::F16;
+    o.x = norm2<IN, OUT_F16>(lo16_op<H16>(x.x), hi16_op<H16>(x.x), w.x, rs); o.y = norm2<IN, OUT_F16>(lo16_op<H16>(x.y), hi16_op<H16>(x.y), w.y, rs);
+    o.z = norm2<IN, OUT_F16>(lo16_op<H16>(x.z), hi16_op<H16>(x.z), w.z, rs); o.w = norm2<IN, OUT_F16>(lo16_op<H16>(x.w), hi16_op<H16>(x.w), w.w, rs);
+    if constexpr (OUT_F16) bad |= h2_nonfinite(o.x) | h2_nonfinite(o.y) | h2_nonfinite(o.z) | h2_nonfinite(o.w);
+  }
   return o;
 }
 
+// NCH > 0: the row is NCH * 64 pieces and stays in registers between the two passes; NCH = 0: any H % 8 == 0, the row is read twice.
 // PW (a handful of rows: the decode step's one-row norms): the weight row is requested together with x, in front of the reduction --
 // a launch that small is one dependent chain, and the weights' L2 round trip otherwise FOLLOWS the reduction (4.6 us per launch at
 // T = 1).  With many rows other waves hide that latency and the 32 extra registers would only cost occupancy, so PW is off there.
-template <int NCH, bool PW = false>
-__global__ void __launch_bounds__(256) rmsnorm_fwd_reg_k(const uint4* __restrict__ x, const uint4* __restrict__ w,
-                                                         uint4* __restrict__ y, int64_t T, int H, float eps) {
+template <RowFmt IN, bool OUT_F16, int NCH, bool PW = false>
+__global__ void __launch_bounds__(256) rmsnorm_fwd_k(const row_piece_t<IN>* __restrict__ x, const out_piece_t<IN>* __restrict__ w,
+                                                     out_piece_t<IN>* __restrict__ y, int64_t T, int H, float eps, unsigned int* ovf) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= T) return;
-  const int HC = H >> 3;
-  const uint4* xr = x + row * HC;
-  uint4 v[NCH], wv[PW ? NCH : 1];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) v[c] = xr[c * 64 + lane];
-  if constexpr (PW) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) wv[c] = w[c * 64 + lane];
-  }
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) ss += sumsq8(v[c]);
-  ss = wave_sum(ss);
-  const float rs = rsqrtf(ss / (float)H + eps);
-  uint4* yr = y + row * HC;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) yr[c * 64 + lane] = norm8(v[c], PW ? wv[c] : w[c * 64 + lane], rs);
-}
-
-__global__ void __launch_bounds__(256) rmsnorm_fwd_generic_k(const uint4* __restrict__ x, const uint4* __restrict__ w,
-                                                             uint4* __restrict__ y, int64_t T, int H, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= T) return;
-  const int HC = H >> 3;
-  const uint4* xr = x + row * HC;
-  float ss = 0.f;
-  for (int c = lane; c < HC; c += 64) ss += sumsq8(xr[c]);
-  ss = wave_sum(ss);
-  const float rs = rsqrtf(ss / (float)H + eps);
-  uint4* yr = y + row * HC;
-  for (int c = lane; c < HC; c += 64) yr[c] = norm8(xr[c], w[c], rs);
-}
-
-// RMSNorm of an fp32 residual stream: x [T,H] fp32 -> y bf16 = bf16(w * (x * rsqrt(mean(x^2) + eps))), ONE rounding (what the reference
-// computes when it runs in fp32, :84-89, rounded once to the bf16 operand the next GEMM takes).  One wave per row; a lane owns the
-// float4 at index c*64 + lane of every 256-element chunk c, so every load instruction covers 1 KiB contiguous and every store 512 B.
-// F16: y = fp16 (the "f16_operands" policy; w stays bf16); a value beyond the fp16 range sets the overflow flag word `ovf`.
-template <int NCH, bool F16 = false>   // H = NCH * 256
-__global__ void __launch_bounds__(256) rmsnorm_fwd_f32in_reg_k(const float4* __restrict__ x, const uint2* __restrict__ w,
-                                                               uint2* __restrict__ y, int64_t T, int H, float eps, unsigned int* ovf) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= T) return;
-  const int HQ = H >> 2;
-  const float4* xr = x + row * HQ;
-  float4 v[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) v[c] = xr[c * 64 + lane];
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
-  ss = wave_sum(ss);
-  const float rs = rsqrtf(ss / (float)H + eps);
-  uint2* yr = y + row * HQ;
+  const int HP = IN == RowFmt::F32 ? H >> 2 : H >> 3;
+  const row_piece_t<IN>* xr = x + row * HP;
+  out_piece_t<IN>* yr = y + row * HP;
   uint32_t bad = 0;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const uint2 ww = w[c * 64 + lane];
-    const uint2 o = make_uint2(pack2_op<F16>(bflo(ww.x) * (v[c].x * rs), bfhi(ww.x) * (v[c].y * rs)),
-                               pack2_op<F16>(bflo(ww.y) * (v[c].z * rs), bfhi(ww.y) * (v[c].w * rs)));
-    if constexpr (F16) bad |= h2_nonfinite(o.x) | h2_nonfinite(o.y);
-    yr[c * 64 + lane] = o;
-  }
-  if constexpr (F16) {
-    if (bad != 0 && ovf != nullptr) atomicOr(ovf, 1u);
-  }
-}
-template <bool F16 = false>
-__global__ void __launch_bounds__(256) rmsnorm_fwd_f32in_generic_k(const float4* __restrict__ x, const uint2* __restrict__ w,
-                                                                   uint2* __restrict__ y, int64_t T, int H, float eps, unsigned int* ovf) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= T) return;
-  const int HQ = H >> 2;
-  const float4* xr = x + row * HQ;
   float ss = 0.f;
-  for (int c = lane; c < HQ; c += 64) { const float4 a = xr[c]; ss += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w; }
-  ss = wave_sum(ss);
-  const float rs = rsqrtf(ss / (float)H + eps);
-  uint2* yr = y + row * HQ;
-  uint32_t bad = 0;
-  for (int c = lane; c < HQ; c += 64) {
-    const float4 a = xr[c];
-    const uint2 ww = w[c];
-    const uint2 o = make_uint2(pack2_op<F16>(bflo(ww.x) * (a.x * rs), bfhi(ww.x) * (a.y * rs)), pack2_op<F16>(bflo(ww.y) * (a.z * rs), bfhi(ww.y) * (a.w * rs)));
-    if constexpr (F16) bad |= h2_nonfinite(o.x) | h2_nonfinite(o.y);
-    yr[c] = o;
-  }
-  if constexpr (F16) {
-    if (bad != 0 && ovf != nullptr) atomicOr(ovf, 1u);
-  }
-}
-
-// RMSNorm of an fp16 residual stream (the "f16_stream" policy): x [T,H] fp16 -> y = round(w * (x * rsqrt(mean(x^2) + eps))) in fp32 with ONE
-// rounding, to fp16 (OUT_F16: the operand of the next GEMM) or to bf16 (last_hidden_state, the pooling kernels' input).  w is bf16.
-template <bool OUT_F16>
-__device__ __forceinline__ uint4 norm8_h16(const uint4& x, const uint4& w, float rs) {
-  uint4 o;
-  o.x = pack2_op<OUT_F16>(bflo(w.x) * (hlo(x.x) * rs), bfhi(w.x) * (hhi(x.x) * rs));
-  o.y = pack2_op<OUT_F16>(bflo(w.y) * (hlo(x.y) * rs), bfhi(w.y) * (hhi(x.y) * rs));
-  o.z = pack2_op<OUT_F16>(bflo(w.z) * (hlo(x.z) * rs), bfhi(w.z) * (hhi(x.z) * rs));
-  o.w = pack2_op<OUT_F16>(bflo(w.w) * (hlo(x.w) * rs), bfhi(w.w) * (hhi(x.w) * rs));
-  return o;
-}
-__device__ __forceinline__ float sumsq8_h16(const uint4& v) {
-  float s = 0.f, a;
-  a = hlo(v.x); s += a * a; a = hhi(v.x); s += a * a;
-  a = hlo(v.y); s += a * a; a = hhi(v.y); s += a * a;
-  a = hlo(v.z); s += a * a; a = hhi(v.z); s += a * a;
-  a = hlo(v.w); s += a * a; a = hhi(v.w); s += a * a;
-  return s;
-}
-template <int NCH, bool OUT_F16>      // NCH > 0: H = NCH * 512, row held in registers; NCH = 0: any H % 8 == 0
-__global__ void __launch_bounds__(256) rmsnorm_fwd_h16_k(const uint4* __restrict__ x, const uint4* __restrict__ w, uint4* __restrict__ y,
-                                                         int64_t T, int H, float eps, unsigned int* ovf) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= T) return;
-  const int HC = H >> 3;
-  const uint4* xr = x + row * HC;
-  uint4* yr = y + row * HC;
-  uint32_t bad = 0;
   if constexpr (NCH > 0) {
-    uint4 v[NCH];
+    row_piece_t<IN> v[NCH];
+    out_piece_t<IN> wv[PW ? NCH : 1];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) v[c] = xr[c * 64 + lane];
-    float ss = 0.f;
+    if constexpr (PW) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) ss += sumsq8_h16(v[c]);
+      for (int c = 0; c < NCH; ++c) wv[c] = w[c * 64 + lane];
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) ss += sumsq<IN>(v[c]);
     ss = wave_sum(ss);
     const float rs = rsqrtf(ss / (float)H + eps);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const uint4 o = norm8_h16<OUT_F16>(v[c], w[c * 64 + lane], rs);
-      if constexpr (OUT_F16) bad |= h2_nonfinite(o.x) | h2_nonfinite(o.y) | h2_nonfinite(o.z) | h2_nonfinite(o.w);
-      yr[c * 64 + lane] = o;
-    }
+    for (int c = 0; c < NCH; ++c) yr[c * 64 + lane] = norm_piece<IN, OUT_F16>(v[c], PW ? wv[c] : w[c * 64 + lane], rs, bad);
   } else {
-    float ss = 0.f;
-    for (int c = lane; c < HC; c += 64) ss += sumsq8_h16(xr[c]);
+    for (int c = lane; c < HP; c += 64) ss += sumsq<IN>(xr[c]);
     ss = wave_sum(ss);
     const float rs = rsqrtf(ss / (float)H + eps);
-    for (int c = lane; c < HC; c += 64) {
-      const uint4 o = norm8_h16<OUT_F16>(xr[c], w[c], rs);
-      if constexpr (OUT_F16) bad |= h2_nonfinite(o.x) | h2_nonfinite(o.y) | h2_nonfinite(o.z) | h2_nonfinite(o.w);
-      yr[c] = o;
-    }
+    for (int c = lane; c < HP; c += 64) yr[c] = norm_piece<IN, OUT_F16>(xr[c], w[c], rs, bad);
   }
   if constexpr (OUT_F16) {
     if (bad != 0 && ovf != nullptr) atomicOr(ovf, 1u);
@@ -346,15 +244,56 @@ __global__ void __launch_bounds__(256) transpose_k(const uint16_t* __restrict__ 
   }
 }
 
-static inline int grid_for(int64_t items, int threads) {
-  int64_t g = (items + threads - 1) / threads;
-  const int64_t cap = 256 * 8;  // 8 blocks per CU, grid-stride the rest
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace grit
 
 using namespace grit;
+
+template <bool F32>
+static int embed_gather_launch(const char* fn, const void* table, const int64_t* ids, void* out, int64_t T, int H, int64_t V, void* stream) {
+  if (T == 0) return GRIT_OK;  // empty batch: nothing to do (empty tensors have null data pointers)
+  GRIT_REQUIRE(table && ids && out, GRIT_E_BADARG, "%s: null pointer", fn);
+  GRIT_REQUIRE(T >= 0 && H > 0 && V > 0, GRIT_E_BADARG, "%s: bad sizes T=%lld H=%d V=%lld", fn, (long long)T, H, (long long)V);
+  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "%s: H=%d must be a multiple of 8", fn, H);
+  GRIT_REQUIRE(aligned16(table) && aligned16(out), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", fn);
+  const int HC = H / 8;
+  hipLaunchKernelGGL(embed_gather_k<F32>, dim3(grid_for(T * HC)), dim3(256), 0, (hipStream_t)stream, (const uint4*)table, ids,
+                     (std::conditional_t<F32, float4, uint4>*)out, T, HC, V);
+  GRIT_CHECK_LAUNCH(fn);
+  return GRIT_OK;
+}
+
+// The one validation block and the one H dispatch of the RMSNorm forward.  with_flag: the entry points of the fp16 policies refuse to
+// run when the device's overflow flag word cannot be reached.
+template <RowFmt IN, bool OUT_F16>
+static int rmsnorm_fwd_launch(const char* fn, bool with_flag, const void* x, const void* w, void* y, int64_t T, int H, float eps, void* stream) {
+  if (T == 0) return GRIT_OK;
+  GRIT_REQUIRE(x && w && y, GRIT_E_BADARG, "%s: null pointer", fn);
+  GRIT_REQUIRE(T >= 0 && H > 0, GRIT_E_BADARG, "%s: bad sizes", fn);
+  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "%s: H=%d must be a multiple of 8", fn, H);
+  GRIT_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", fn);
+  unsigned int* ovf = with_flag ? f16_flag_ptr() : nullptr;
+  GRIT_REQUIRE(!with_flag || ovf != nullptr, GRIT_E_LAUNCH, "%s: the overflow flag word of this device is not reachable", fn);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const row_piece_t<IN>*)x,
+                       (const out_piece_t<IN>*)w, (out_piece_t<IN>*)y, T, H, eps, ovf);
+  };
+  constexpr int ROW = IN == RowFmt::F32 ? 256 : 512;   // elements that 64 lanes cover with one piece each
+  switch (H % ROW == 0 ? H / ROW : 0) {
+    case 1: launch(rmsnorm_fwd_k<IN, OUT_F16, 1>); break;
+    case 2: launch(rmsnorm_fwd_k<IN, OUT_F16, 2>); break;
+    case 4: launch(rmsnorm_fwd_k<IN, OUT_F16, 4>); break;
+    case 8:
+      if constexpr (IN == RowFmt::BF16) {
+        if (T <= 16) { launch(rmsnorm_fwd_k<IN, OUT_F16, 8, true>); break; }
+      }
+      launch(rmsnorm_fwd_k<IN, OUT_F16, 8>);
+      break;
+    case 16: launch(rmsnorm_fwd_k<IN, OUT_F16, 16>); break;
+    default: launch(rmsnorm_fwd_k<IN, OUT_F16, 0>); break;
+  }
+  GRIT_CHECK_LAUNCH(fn);
+  return GRIT_OK;
+}
 
 extern "C" {
 
@@ -362,142 +301,27 @@ int grit_version(void) { return GRIT_ABI_VERSION; }
 const char* grit_last_error_string(void) { return g_err; }
 
 int grit_embed_gather(const void* table, const int64_t* ids, void* out, int64_t T, int H, int64_t V, void* stream) {
-  if (T == 0) return GRIT_OK;  // empty batch: nothing to do (empty tensors have null data pointers)
-  GRIT_REQUIRE(table && ids && out, GRIT_E_BADARG, "grit_embed_gather: null pointer");
-  GRIT_REQUIRE(T >= 0 && H > 0 && V > 0, GRIT_E_BADARG, "grit_embed_gather: bad sizes T=%lld H=%d V=%lld", (long long)T, H, (long long)V);
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_embed_gather: H=%d must be a multiple of 8", H);
-  GRIT_REQUIRE(aligned16(table) && aligned16(out), GRIT_E_BADARG, "grit_embed_gather: pointers must be 16-byte aligned");
-  if (T == 0) return GRIT_OK;
-  const int HC = H / 8;
-  hipLaunchKernelGGL(embed_gather_k, dim3(grid_for(T * HC, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)table, ids,
-                     (uint4*)out, T, HC, V);
-  GRIT_CHECK_LAUNCH("grit_embed_gather");
-  return GRIT_OK;
+  return embed_gather_launch<false>("grit_embed_gather", table, ids, out, T, H, V, stream);
+}
+int grit_embed_gather_f32(const void* table, const int64_t* ids, float* out, int64_t T, int H, int64_t V, void* stream) {
+  return embed_gather_launch<true>("grit_embed_gather_f32", table, ids, out, T, H, V, stream);
 }
 
 int grit_rmsnorm_fwd(const void* x, const void* w, void* y, int64_t T, int H, float eps, void* stream) {
-  if (T == 0) return GRIT_OK;
-  GRIT_REQUIRE(x && w && y, GRIT_E_BADARG, "grit_rmsnorm_fwd: null pointer");
-  GRIT_REQUIRE(T >= 0 && H > 0, GRIT_E_BADARG, "grit_rmsnorm_fwd: bad sizes");
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_rmsnorm_fwd: H=%d must be a multiple of 8", H);
-  GRIT_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), GRIT_E_BADARG, "grit_rmsnorm_fwd: pointers must be 16-byte aligned");
-  if (T == 0) return GRIT_OK;
-  const dim3 grid((unsigned)((T + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const uint4 *xp = (const uint4*)x, *wp = (const uint4*)w;
-  uint4* yp = (uint4*)y;
-  if (H % 512 == 0 && H / 512 <= 16) {
-    switch (H / 512) {
-      case 1: hipLaunchKernelGGL(rmsnorm_fwd_reg_k<1>, grid, block, 0, st, xp, wp, yp, T, H, eps); break;
-      case 2: hipLaunchKernelGGL(rmsnorm_fwd_reg_k<2>, grid, block, 0, st, xp, wp, yp, T, H, eps); break;
-      case 4: hipLaunchKernelGGL(rmsnorm_fwd_reg_k<4>, grid, block, 0, st, xp, wp, yp, T, H, eps); break;
-      case 8:
-        if (T <= 16) hipLaunchKernelGGL((rmsnorm_fwd_reg_k<8, true>), grid, block, 0, st, xp, wp, yp, T, H, eps);
-        else hipLaunchKernelGGL(rmsnorm_fwd_reg_k<8>, grid, block, 0, st, xp, wp, yp, T, H, eps);
-        break;
-      case 16: hipLaunchKernelGGL(rmsnorm_fwd_reg_k<16>, grid, block, 0, st, xp, wp, yp, T, H, eps); break;
-      default: hipLaunchKernelGGL(rmsnorm_fwd_generic_k, grid, block, 0, st, xp, wp, yp, T, H, eps); break;
-    }
-  } else {
-    hipLaunchKernelGGL(rmsnorm_fwd_generic_k, grid, block, 0, st, xp, wp, yp, T, H, eps);
-  }
-  GRIT_CHECK_LAUNCH("grit_rmsnorm_fwd");
-  return GRIT_OK;
+  return rmsnorm_fwd_launch<RowFmt::BF16, false>("grit_rmsnorm_fwd", false, x, w, y, T, H, eps, stream);
 }
-
-int grit_embed_gather_f32(const void* table, const int64_t* ids, float* out, int64_t T, int H, int64_t V, void* stream) {
-  if (T == 0) return GRIT_OK;
-  GRIT_REQUIRE(table && ids && out, GRIT_E_BADARG, "grit_embed_gather_f32: null pointer");
-  GRIT_REQUIRE(T >= 0 && H > 0 && V > 0, GRIT_E_BADARG, "grit_embed_gather_f32: bad sizes T=%lld H=%d V=%lld", (long long)T, H, (long long)V);
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_embed_gather_f32: H=%d must be a multiple of 8", H);
-  GRIT_REQUIRE(aligned16(table) && aligned16(out), GRIT_E_BADARG, "grit_embed_gather_f32: pointers must be 16-byte aligned");
-  const int HC = H / 8;
-  hipLaunchKernelGGL(embed_gather_f32_k, dim3(grid_for(T * HC, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)table, ids,
-                     (float4*)out, T, HC, V);
-  GRIT_CHECK_LAUNCH("grit_embed_gather_f32");
-  return GRIT_OK;
-}
-
 int grit_rmsnorm_fwd_f32in(const float* x, const void* w, void* y, int64_t T, int H, float eps, void* stream) {
-  if (T == 0) return GRIT_OK;
-  GRIT_REQUIRE(x && w && y, GRIT_E_BADARG, "grit_rmsnorm_fwd_f32in: null pointer");
-  GRIT_REQUIRE(T >= 0 && H > 0, GRIT_E_BADARG, "grit_rmsnorm_fwd_f32in: bad sizes");
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_rmsnorm_fwd_f32in: H=%d must be a multiple of 8", H);
-  GRIT_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), GRIT_E_BADARG, "grit_rmsnorm_fwd_f32in: pointers must be 16-byte aligned");
-  const dim3 grid((unsigned)((T + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const float4* xp = (const float4*)x;
-  const uint2* wp = (const uint2*)w;
-  uint2* yp = (uint2*)y;
-  switch (H % 256 == 0 ? H / 256 : 0) {
-    case 1: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<1, false>), grid, block, 0, st, xp, wp, yp, T, H, eps, (unsigned int*)nullptr); break;
-    case 2: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<2, false>), grid, block, 0, st, xp, wp, yp, T, H, eps, (unsigned int*)nullptr); break;
-    case 4: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<4, false>), grid, block, 0, st, xp, wp, yp, T, H, eps, (unsigned int*)nullptr); break;
-    case 8: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<8, false>), grid, block, 0, st, xp, wp, yp, T, H, eps, (unsigned int*)nullptr); break;
-    case 16: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<16, false>), grid, block, 0, st, xp, wp, yp, T, H, eps, (unsigned int*)nullptr); break;
-    default: hipLaunchKernelGGL(rmsnorm_fwd_f32in_generic_k<false>, grid, block, 0, st, xp, wp, yp, T, H, eps, (unsigned int*)nullptr); break;
-  }
-  GRIT_CHECK_LAUNCH("grit_rmsnorm_fwd_f32in");
-  return GRIT_OK;
+  return rmsnorm_fwd_launch<RowFmt::F32, false>("grit_rmsnorm_fwd_f32in", false, x, w, y, T, H, eps, stream);
 }
-
 /* fp16-operand policy: the same RMSNorm of the fp32 residual stream, y rounded once to IEEE fp16 (w stays bf16) */
 int grit_rmsnorm_fwd_f32in_f16(const float* x, const void* w, void* y, int64_t T, int H, float eps, void* stream) {
-  if (T == 0) return GRIT_OK;
-  GRIT_REQUIRE(x && w && y, GRIT_E_BADARG, "grit_rmsnorm_fwd_f32in_f16: null pointer");
-  GRIT_REQUIRE(T >= 0 && H > 0, GRIT_E_BADARG, "grit_rmsnorm_fwd_f32in_f16: bad sizes");
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_rmsnorm_fwd_f32in_f16: H=%d must be a multiple of 8", H);
-  GRIT_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), GRIT_E_BADARG, "grit_rmsnorm_fwd_f32in_f16: pointers must be 16-byte aligned");
-  unsigned int* ovf = f16_flag_ptr();
-  GRIT_REQUIRE(ovf != nullptr, GRIT_E_LAUNCH, "grit_rmsnorm_fwd_f32in_f16: the overflow flag word of this device is not reachable");
-  const dim3 grid((unsigned)((T + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const float4* xp = (const float4*)x;
-  const uint2* wp = (const uint2*)w;
-  uint2* yp = (uint2*)y;
-  switch (H % 256 == 0 ? H / 256 : 0) {
-    case 1: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<1, true>), grid, block, 0, st, xp, wp, yp, T, H, eps, ovf); break;
-    case 2: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<2, true>), grid, block, 0, st, xp, wp, yp, T, H, eps, ovf); break;
-    case 4: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<4, true>), grid, block, 0, st, xp, wp, yp, T, H, eps, ovf); break;
-    case 8: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<8, true>), grid, block, 0, st, xp, wp, yp, T, H, eps, ovf); break;
-    case 16: hipLaunchKernelGGL((rmsnorm_fwd_f32in_reg_k<16, true>), grid, block, 0, st, xp, wp, yp, T, H, eps, ovf); break;
-    default: hipLaunchKernelGGL(rmsnorm_fwd_f32in_generic_k<true>, grid, block, 0, st, xp, wp, yp, T, H, eps, ovf); break;
-  }
-  GRIT_CHECK_LAUNCH("grit_rmsnorm_fwd_f32in_f16");
-  return GRIT_OK;
+  return rmsnorm_fwd_launch<RowFmt::F32, true>("grit_rmsnorm_fwd_f32in_f16", true, x, w, y, T, H, eps, stream);
 }
-
 /* fp16 residual stream (the "f16_stream" policy): MistralRMSNorm (:84-89) of an fp16 row, ONE rounding; y fp16 (out_is_f16 != 0: the next
  * GEMM's operand) or bf16 (last_hidden_state for the pooling kernels); w bf16 */
 int grit_rmsnorm_fwd_f16in(const void* x, const void* w, void* y, int out_is_f16, int64_t T, int H, float eps, void* stream) {
-  if (T == 0) return GRIT_OK;
-  GRIT_REQUIRE(x && w && y, GRIT_E_BADARG, "grit_rmsnorm_fwd_f16in: null pointer");
-  GRIT_REQUIRE(T >= 0 && H > 0, GRIT_E_BADARG, "grit_rmsnorm_fwd_f16in: bad sizes");
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_rmsnorm_fwd_f16in: H=%d must be a multiple of 8", H);
-  GRIT_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), GRIT_E_BADARG, "grit_rmsnorm_fwd_f16in: pointers must be 16-byte aligned");
-  unsigned int* ovf = f16_flag_ptr();
-  GRIT_REQUIRE(ovf != nullptr, GRIT_E_LAUNCH, "grit_rmsnorm_fwd_f16in: the overflow flag word of this device is not reachable");
-  const dim3 grid((unsigned)((T + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const uint4* xp = (const uint4*)x;
-  const uint4* wp = (const uint4*)w;
-  uint4* yp = (uint4*)y;
-#define GRIT_H16(NCH_)                                                                                                     \
-  do {                                                                                                                     \
-    if (out_is_f16) hipLaunchKernelGGL((rmsnorm_fwd_h16_k<NCH_, true>), grid, block, 0, st, xp, wp, yp, T, H, eps, ovf);   \
-    else hipLaunchKernelGGL((rmsnorm_fwd_h16_k<NCH_, false>), grid, block, 0, st, xp, wp, yp, T, H, eps, ovf);             \
-  } while (0)
-  switch (H % 512 == 0 ? H / 512 : 0) {
-    case 1: GRIT_H16(1); break;
-    case 2: GRIT_H16(2); break;
-    case 4: GRIT_H16(4); break;
-    case 8: GRIT_H16(8); break;
-    case 16: GRIT_H16(16); break;
-    default: GRIT_H16(0); break;
-  }
-#undef GRIT_H16
-  GRIT_CHECK_LAUNCH("grit_rmsnorm_fwd_f16in");
-  return GRIT_OK;
+  return out_is_f16 ? rmsnorm_fwd_launch<RowFmt::F16, true>("grit_rmsnorm_fwd_f16in", true, x, w, y, T, H, eps, stream)
+                    : rmsnorm_fwd_launch<RowFmt::F16, false>("grit_rmsnorm_fwd_f16in", true, x, w, y, T, H, eps, stream);
 }
 
 /* The current device's fp16 overflow flag: *host_flag = 1 when a kernel of the f16_operands policy has stored an inf / nan since the last
@@ -545,7 +369,7 @@ static int rope_launch(void* qkv, const float* cos_tab, const float* sin_tab, co
   if (T == 0) return GRIT_OK;
   const int nheads = nq + nkv;
   const int64_t items = T * nheads * (d / 16);
-  hipLaunchKernelGGL(rope_k, dim3(grid_for(items, 256)), dim3(256), 0, (hipStream_t)stream, (uint16_t*)qkv,
+  hipLaunchKernelGGL(rope_k, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, (uint16_t*)qkv,
                      (const float4*)cos_tab, (const float4*)sin_tab, positions, T, S, nheads, d, row_stride, inverse ? -1.0f : 1.0f);
   GRIT_CHECK_LAUNCH("grit_rope_qk_inplace");
   return GRIT_OK;

@@ -5,14 +5,39 @@
 //   combine : out = residual + (w_a * y_a  (+)  w_b * y_b) with the reference's bf16 rounding points (:876, :880, decoder :945)
 // The expert MLPs themselves are two launches of grit_gemm_bf16_nt_grouped (gathered A rows, SwiGLU epilogue; then w2).
 // All three kernels are HBM/latency-bound byte work; no MFMA.
-#include <atomic>
-
 #include "common.h"
 
 namespace grit {
 
 constexpr int MOE_MAX_E = 16;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+
+// ---- softmax over a token's E logits (fp32), top-2, renormalise: the tail of both routers
+struct Top2 { int e0, e1; float w0, w1; bool nonfinite; };
+template <int E>
+__device__ __forceinline__ Top2 top2_select(const float (&logit)[E]) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int e = 0; e < E; ++e) mx = fmaxf(mx, logit[e]);
+  float p[E], den = 0.f;
+#pragma unroll
+  for (int e = 0; e < E; ++e) { p[e] = expf(logit[e] - mx); den += p[e]; }
+  int e0 = 0, e1 = 1;
+  float p0 = -1.f, p1 = -1.f;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {                    // descending, lowest index first on ties (the oracle's stable argsort)
+    const float pe = p[e] / den;
+    if (pe > p0) { p1 = p0; e1 = e0; p0 = pe; e0 = e; }
+    else if (pe > p1) { p1 = pe; e1 = e; }
+  }
+  // a non-finite softmax (a NaN or +inf logit, or every logit -inf: den is NaN) makes every compare above false; such a row takes
+  // experts (0, 1) at (0.5, 0.5) -- the oracle's stable argsort puts NaN last -- so that no consumer ever sees an index outside [0, E).
+  // Finite rows: den is in [1, E] and the selection above is untouched.
+  const bool nonfinite = !__builtin_isfinite(den);
+  if (nonfinite) { e0 = 0; e1 = 1; p0 = 0.5f; p1 = 0.5f; }
+  const float s = p0 + p1;
+  return {e0, e1, p0 / s, p1 / s, nonfinite};
+}
 
 // ---- router: one wave per token, gate weights staged in LDS ([E,H] bf16)
 template <int E>
@@ -52,29 +77,12 @@ __global__ void __launch_bounds__(256) moe_router_top2_k(const uint16_t* __restr
         }
       }
     }
-    float mx = -INFINITY;
 #pragma unroll
-    for (int e = 0; e < E; ++e) { acc[e] = round_bf(wave_sum(acc[e])); mx = fmaxf(mx, acc[e]); }   // nn.Linear output in the model dtype
-    float p[E], den = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) { p[e] = expf(acc[e] - mx); den += p[e]; }
-    int e0 = 0, e1 = 1;
-    float p0 = -1.f, p1 = -1.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {                    // descending, lowest index first on ties (the oracle's stable argsort)
-      const float pe = p[e] / den;
-      if (pe > p0) { p1 = p0; e1 = e0; p0 = pe; e0 = e; }
-      else if (pe > p1) { p1 = pe; e1 = e; }
-    }
-    // a non-finite softmax (a NaN or +inf logit, or every logit -inf: den is NaN) makes every compare above false; such a row takes
-    // experts (0, 1) at (0.5, 0.5) -- the oracle's stable argsort puts NaN last -- so that no consumer ever sees an index outside [0, E).
-    // Finite rows: den is in [1, E] and the selection above is untouched.
-    const bool nonfinite = !__builtin_isfinite(den);
-    if (nonfinite) { e0 = 0; e1 = 1; p0 = 0.5f; p1 = 0.5f; }
+    for (int e = 0; e < E; ++e) acc[e] = round_bf(wave_sum(acc[e]));   // nn.Linear output in the model dtype
+    const Top2 r = top2_select<E>(acc);
     if (lane == 0) {
-      const float s = p0 + p1;
-      experts[2 * t] = e0; experts[2 * t + 1] = e1;
-      weights[2 * t] = round_bf(p0 / s); weights[2 * t + 1] = round_bf(p1 / s);
+      experts[2 * t] = r.e0; experts[2 * t + 1] = r.e1;
+      weights[2 * t] = round_bf(r.w0); weights[2 * t + 1] = round_bf(r.w1);
     }
   }
 }
@@ -123,30 +131,13 @@ __global__ void __launch_bounds__(256) moe_router_top2_f32_k(const float* __rest
       }
     }
     const float inv = rsqrtf(wave_sum(ss) / (float)H + eps);
-    float mx = -INFINITY;
 #pragma unroll
-    for (int e = 0; e < E; ++e) { acc[e] = wave_sum(acc[e]) * inv; mx = fmaxf(mx, acc[e]); }
-    float p[E], den = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) { p[e] = expf(acc[e] - mx); den += p[e]; }
-    int e0 = 0, e1 = 1;
-    float p0 = -1.f, p1 = -1.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {                    // descending, lowest index first on ties (the oracle's stable argsort)
-      const float pe = p[e] / den;
-      if (pe > p0) { p1 = p0; e1 = e0; p0 = pe; e0 = e; }
-      else if (pe > p1) { p1 = pe; e1 = e; }
-    }
-    // a non-finite softmax (a NaN or +inf logit, or every logit -inf: den is NaN) makes every compare above false; such a row takes
-    // experts (0, 1) at (0.5, 0.5) -- the oracle's stable argsort puts NaN last -- so that no consumer ever sees an index outside [0, E).
-    // Finite rows: den is in [1, E] and the selection above is untouched.
-    const bool nonfinite = !__builtin_isfinite(den);
-    if (nonfinite) { e0 = 0; e1 = 1; p0 = 0.5f; p1 = 0.5f; }
+    for (int e = 0; e < E; ++e) acc[e] = wave_sum(acc[e]) * inv;
+    const Top2 r = top2_select<E>(acc);
     if (lane == 0) {
-      const float s = p0 + p1;
-      experts[2 * t] = e0; experts[2 * t + 1] = e1;
-      weights[2 * t] = p0 / s; weights[2 * t + 1] = p1 / s;
-      if (nonfinite) atomicOr(ovf, 1u);            // the policy's overflow reached the router: report it even if no fp16 store saw it
+      experts[2 * t] = r.e0; experts[2 * t + 1] = r.e1;
+      weights[2 * t] = r.w0; weights[2 * t + 1] = r.w1;
+      if (r.nonfinite) atomicOr(ovf, 1u);          // the policy's overflow reached the router: report it even if no fp16 store saw it
     }
   }
 }
@@ -450,19 +441,6 @@ __global__ void __launch_bounds__(256) moe_combine_bwd_k(const uint16_t* __restr
 
 using namespace grit;
 
-// A dynamic-LDS opt-in is a PER-DEVICE function attribute: set once per (kernel, device), from whichever thread gets there first
-// (autograd worker threads call into the backward entry points concurrently).
-template <typename KernelT>
-static void lds_optin_once(KernelT kernel, std::atomic<uint64_t>& done, int bytes) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done.fetch_or(bit, std::memory_order_release);
-  }
-}
-
 extern "C" int grit_moe_combine_bwd(const void* dout, const void* y, const int32_t* row_token, const int32_t* rows, const float* weights,
                                     void* dy, float* dw, int64_t T, int H, void* stream) {
   if (T == 0) return GRIT_OK;
@@ -488,14 +466,11 @@ extern "C" int grit_moe_router_top2(const void* x, const void* gate_w, int32_t* 
   int64_t nb = (T + 3) / 4;
   if (nb > 1024) nb = 1024;
   hipStream_t st = (hipStream_t)stream;
-#define GRIT_ROUTER(E_)                                                                                                       \
-  do {                                                                                                                        \
-    static std::atomic<uint64_t> optin_{0};                                                                                   \
-    lds_optin_once(moe_router_top2_k<E_>, optin_, 160 * 1024);                                                                \
-    hipLaunchKernelGGL(moe_router_top2_k<E_>, dim3((unsigned)nb), dim3(256), lds, st, (const uint16_t*)x, (const uint16_t*)gate_w, T, H,  \
-                       experts, weights);                                                                                     \
-  } while (0)
-  if (E == 4) GRIT_ROUTER(4); else if (E == 8) GRIT_ROUTER(8); else GRIT_ROUTER(16);
+  with_experts(E, [&](auto e) {
+    constexpr auto kernel = moe_router_top2_k<decltype(e)::value>;
+    lds_optin_once<kernel>(160 * 1024);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), lds, st, (const uint16_t*)x, (const uint16_t*)gate_w, T, H, experts, weights);
+  });
   GRIT_CHECK_LAUNCH("grit_moe_router_top2");
   return GRIT_OK;
 }
@@ -516,14 +491,12 @@ extern "C" int grit_moe_router_top2_f32(const float* h, const void* ln_w, float 
   int64_t nb = (T + 3) / 4;
   if (nb > 2048) nb = 2048;
   hipStream_t st = (hipStream_t)stream;
-#define GRIT_ROUTER32(E_)                                                                                                     \
-  do {                                                                                                                        \
-    static std::atomic<uint64_t> optin_{0};                                                                                   \
-    lds_optin_once(moe_router_top2_f32_k<E_>, optin_, 160 * 1024);                                                            \
-    hipLaunchKernelGGL(moe_router_top2_f32_k<E_>, dim3((unsigned)nb), dim3(256), lds, st, h, (const uint16_t*)ln_w, eps,      \
-                       (const uint16_t*)gate_w, T, H, experts, weights, ovf);                                                 \
-  } while (0)
-  if (E == 4) GRIT_ROUTER32(4); else if (E == 8) GRIT_ROUTER32(8); else GRIT_ROUTER32(16);
+  with_experts(E, [&](auto e) {
+    constexpr auto kernel = moe_router_top2_f32_k<decltype(e)::value>;
+    lds_optin_once<kernel>(160 * 1024);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), lds, st, h, (const uint16_t*)ln_w, eps, (const uint16_t*)gate_w, T, H, experts,
+                       weights, ovf);
+  });
   GRIT_CHECK_LAUNCH("grit_moe_router_top2_f32");
   return GRIT_OK;
 }
@@ -559,14 +532,12 @@ extern "C" int grit_moe_router_bwd(const void* x, const void* gate_w, const int3
   int64_t nb = (T + 3) / 4;
   if (nb > 1024) nb = 1024;
   hipStream_t st = (hipStream_t)stream;
-#define GRIT_ROUTER_BWD(E_)                                                                                                   \
-  do {                                                                                                                        \
-    static std::atomic<uint64_t> optin_{0};                                                                                   \
-    lds_optin_once(moe_router_bwd_k<E_>, optin_, 160 * 1024);                                                                 \
-    hipLaunchKernelGGL(moe_router_bwd_k<E_>, dim3((unsigned)nb), dim3(256), lds, st, (const uint16_t*)x, (const uint16_t*)gate_w, experts, dw, \
-                       aux_dlogits, (const uint16_t*)dx_in, (uint16_t*)dx_out, dlogits, T, H);                                \
-  } while (0)
-  if (E == 4) GRIT_ROUTER_BWD(4); else if (E == 8) GRIT_ROUTER_BWD(8); else GRIT_ROUTER_BWD(16);
+  with_experts(E, [&](auto e) {
+    constexpr auto kernel = moe_router_bwd_k<decltype(e)::value>;
+    lds_optin_once<kernel>(160 * 1024);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), lds, st, (const uint16_t*)x, (const uint16_t*)gate_w, experts, dw, aux_dlogits,
+                       (const uint16_t*)dx_in, (uint16_t*)dx_out, dlogits, T, H);
+  });
   GRIT_CHECK_LAUNCH("grit_moe_router_bwd");
   return GRIT_OK;
 }
@@ -586,9 +557,9 @@ extern "C" int grit_moe_router_wgrad(const void* x, const float* dlogits, void* 
   GRIT_REQUIRE(nslab <= 65535, GRIT_E_UNSUPPORTED, "grit_moe_router_wgrad: T=%lld exceeds 65535 slabs of %d tokens", (long long)T, RW_SLAB);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((H / 2 + 255) / 256), (unsigned)nslab);
-  if (E == 4) hipLaunchKernelGGL(moe_router_wgrad_k<4>, grid, dim3(256), 0, st, (const uint16_t*)x, dlogits, workspace, T, H);
-  else if (E == 8) hipLaunchKernelGGL(moe_router_wgrad_k<8>, grid, dim3(256), 0, st, (const uint16_t*)x, dlogits, workspace, T, H);
-  else hipLaunchKernelGGL(moe_router_wgrad_k<16>, grid, dim3(256), 0, st, (const uint16_t*)x, dlogits, workspace, T, H);
+  with_experts(E, [&](auto e) {
+    hipLaunchKernelGGL(moe_router_wgrad_k<decltype(e)::value>, grid, dim3(256), 0, st, (const uint16_t*)x, dlogits, workspace, T, H);
+  });
   GRIT_CHECK_LAUNCH("grit_moe_router_wgrad");
   const int64_t EH = (int64_t)E * H;
   hipLaunchKernelGGL(moe_router_wgrad_reduce_k, dim3((unsigned)((EH + 255) / 256)), dim3(256), 0, st, (const float*)workspace, (uint16_t*)grad,

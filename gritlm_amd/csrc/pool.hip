@@ -6,8 +6,6 @@
 // 1 KiB per wave-instruction), skips rows whose pooling weight is zero (padding / instruction tokens are
 // never read), accumulates in fp32 registers and normalises in the same launch.  HBM-bound:
 // algorithmic bytes = B*S*H*2 read + B*H*4 written.
-#include <atomic>
-
 #include "common.h"
 
 namespace grit {
@@ -76,6 +74,72 @@ __device__ __forceinline__ void fma8(float (&a)[8], const uint4& v, float w) {
   a[4] += w * bflo(v.z); a[5] += w * bfhi(v.z); a[6] += w * bflo(v.w); a[7] += w * bfhi(v.w);
 }
 
+// a += sum over k in [k0, k1) of wt(k) * (16-byte piece cc of row row(k)); the caller says which row and which weight entry k has
+template <typename RowF, typename WtF>
+__device__ __forceinline__ void pool_accumulate(float (&a)[8], const uint4* __restrict__ hb, int HC, int cc, int k0, int k1, RowF row, WtF wt) {
+  int k = k0;
+  for (; k + 8 <= k1; k += 8) {  // 8 row loads (128 B) in flight per lane: one workgroup per CU has to cover the HBM latency alone
+    uint4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = hb[(int64_t)row(k + u) * HC + cc];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) fma8(a, v[u], wt(k + u));       // same accumulation order as one row at a time
+  }
+  for (; k + 4 <= k1; k += 4) {
+    const uint4 v0 = hb[(int64_t)row(k) * HC + cc], v1 = hb[(int64_t)row(k + 1) * HC + cc];
+    const uint4 v2 = hb[(int64_t)row(k + 2) * HC + cc], v3 = hb[(int64_t)row(k + 3) * HC + cc];
+    fma8(a, v0, wt(k)); fma8(a, v1, wt(k + 1)); fma8(a, v2, wt(k + 2)); fma8(a, v3, wt(k + 3));
+  }
+  for (; k < k1; ++k) fma8(a, hb[(int64_t)row(k) * HC + cc], wt(k));
+}
+
+// One document of the forward, both layouts: ob[:] = (weighted row sum) / den, then L2-normalised in place when `normalize`.
+// red: POOL_THREADS / 64 floats of LDS.
+template <typename RowF, typename WtF>
+__device__ __forceinline__ void pool_reduce_normalize(const uint4* __restrict__ hb, int H, int k0, int k1, RowF row, WtF wt, float den,
+                                                      float* __restrict__ ob, float* __restrict__ inv_norm_b, int normalize, float* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int HC = H >> 3;
+  float ssq = 0.f;
+  for (int cc = tid; cc < HC; cc += POOL_THREADS) {
+    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    pool_accumulate(a, hb, HC, cc, k0, k1, row, wt);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { a[e] = a[e] / den; ssq += a[e] * a[e]; }
+    float4* o4 = reinterpret_cast<float4*>(ob + cc * 8);
+    o4[0] = make_float4(a[0], a[1], a[2], a[3]);
+    o4[1] = make_float4(a[4], a[5], a[6], a[7]);
+  }
+  if (!normalize) {
+    if (inv_norm_b && tid == 0) *inv_norm_b = 1.f;
+    return;
+  }
+  ssq = wave_sum(ssq);
+  if (lane == 0) red[wave] = ssq;
+  __syncthreads();
+  float tot = 0.f;
+#pragma unroll
+  for (int w = 0; w < POOL_THREADS / 64; ++w) tot += red[w];
+  const float inv = 1.0f / fmaxf(sqrtf(tot), 1e-12f);  // F.normalize eps
+  if (inv_norm_b && tid == 0) *inv_norm_b = inv;
+  for (int cc = tid; cc < HC; cc += POOL_THREADS) {  // each thread rescales what it wrote itself
+    float4* o4 = reinterpret_cast<float4*>(ob + cc * 8);
+    float4 x = o4[0], y = o4[1];
+    x.x *= inv; x.y *= inv; x.z *= inv; x.w *= inv; y.x *= inv; y.y *= inv; y.z *= inv; y.w *= inv;
+    o4[0] = x; o4[1] = y;
+  }
+}
+
+// Pooled rows [s0, s1) of a packed document of `len` rows whose first `instr` are not pooled, and the denominator (both directions)
+struct PackedSpan { int s0, s1; float den; };
+__device__ __forceinline__ PackedSpan packed_span(int len, int instr, int mode) {
+  PackedSpan p = {instr, len, (float)(len - instr)};
+  if (mode == GRIT_POOL_WEIGHTEDMEAN) { const float n = (float)(len - instr); p.den = 0.5f * n * (n + 1.f); }
+  if (mode == GRIT_POOL_CLS) { p.s0 = 0; p.s1 = len > 0 ? 1 : 0; p.den = 1.f; }
+  if (mode == GRIT_POOL_LASTTOKEN) { p.s0 = len > 0 ? len - 1 : 0; p.s1 = len; p.den = 1.f; }
+  return p;
+}
+
 __global__ void __launch_bounds__(POOL_THREADS) pool_norm_fwd_k(const uint16_t* __restrict__ hidden, const int64_t* __restrict__ mask,
                                                                 const int32_t* __restrict__ instr_len, float* __restrict__ out,
                                                                 float* __restrict__ inv_norm, int S, int H, int mode, int normalize) {
@@ -86,55 +150,12 @@ __global__ void __launch_bounds__(POOL_THREADS) pool_norm_fwd_k(const uint16_t* 
   int* nzp = reinterpret_cast<int*>(red + 8);
   float* denp = red + 9;
 
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (wave == 0) pool_weights(mask + (int64_t)b * S, instr_len ? instr_len[b] : 0, S, mode, cs, cw, nzp, denp);
+  const int b = blockIdx.x;
+  if ((threadIdx.x >> 6) == 0) pool_weights(mask + (int64_t)b * S, instr_len ? instr_len[b] : 0, S, mode, cs, cw, nzp, denp);
   __syncthreads();
-  const int nz = *nzp;
-  const float den = *denp;  // den == 0 -> NaN/inf rows exactly like the unguarded reference (:213-214)
-  const int HC = H >> 3;
-  const uint4* hb = reinterpret_cast<const uint4*>(hidden + (int64_t)b * S * H);
-  float* ob = out + (int64_t)b * H;
-  float ssq = 0.f;
-  for (int cc = tid; cc < HC; cc += POOL_THREADS) {
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int k = 0;
-    for (; k + 8 <= nz; k += 8) {  // 8 row loads (128 B) in flight per lane: one workgroup per CU has to cover the HBM latency alone
-      uint4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = hb[(int64_t)cs[k + u] * HC + cc];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) fma8(a, v[u], cw[k + u]);       // same accumulation order as one row at a time
-    }
-    for (; k + 4 <= nz; k += 4) {
-      const uint4 v0 = hb[(int64_t)cs[k] * HC + cc], v1 = hb[(int64_t)cs[k + 1] * HC + cc];
-      const uint4 v2 = hb[(int64_t)cs[k + 2] * HC + cc], v3 = hb[(int64_t)cs[k + 3] * HC + cc];
-      fma8(a, v0, cw[k]); fma8(a, v1, cw[k + 1]); fma8(a, v2, cw[k + 2]); fma8(a, v3, cw[k + 3]);
-    }
-    for (; k < nz; ++k) fma8(a, hb[(int64_t)cs[k] * HC + cc], cw[k]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { a[e] = a[e] / den; ssq += a[e] * a[e]; }
-    float4* o4 = reinterpret_cast<float4*>(ob + cc * 8);
-    o4[0] = make_float4(a[0], a[1], a[2], a[3]);
-    o4[1] = make_float4(a[4], a[5], a[6], a[7]);
-  }
-  if (!normalize) {
-    if (inv_norm && tid == 0) inv_norm[b] = 1.f;
-    return;
-  }
-  ssq = wave_sum(ssq);
-  if (lane == 0) red[wave] = ssq;
-  __syncthreads();
-  float tot = 0.f;
-#pragma unroll
-  for (int w = 0; w < POOL_THREADS / 64; ++w) tot += red[w];
-  const float inv = 1.0f / fmaxf(sqrtf(tot), 1e-12f);  // F.normalize eps
-  if (inv_norm && tid == 0) inv_norm[b] = inv;
-  for (int cc = tid; cc < HC; cc += POOL_THREADS) {  // each thread rescales what it wrote itself
-    float4* o4 = reinterpret_cast<float4*>(ob + cc * 8);
-    float4 x = o4[0], y = o4[1];
-    x.x *= inv; x.y *= inv; x.z *= inv; x.w *= inv; y.x *= inv; y.y *= inv; y.z *= inv; y.w *= inv;
-    o4[0] = x; o4[1] = y;
-  }
+  // den == 0 -> NaN/inf rows exactly like the unguarded reference (:213-214)
+  pool_reduce_normalize(reinterpret_cast<const uint4*>(hidden + (int64_t)b * S * H), H, 0, *nzp, [cs](int k) { return cs[k]; },
+                        [cw](int k) { return cw[k]; }, *denp, out + (int64_t)b * H, inv_norm ? inv_norm + b : nullptr, normalize, red);
 }
 
 // Packed (un-padded) batches: document b occupies rows [cu[b], cu[b+1]) of hidden [T,H]; every row is a real token, the first
@@ -143,62 +164,45 @@ __global__ void __launch_bounds__(POOL_THREADS) pool_norm_varlen_fwd_k(const uin
                                                                        const int32_t* __restrict__ instr_len, float* __restrict__ out,
                                                                        float* __restrict__ inv_norm, int H, int mode, int normalize) {
   __shared__ float red[POOL_THREADS / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
   const int64_t start = cu[b];
   const int len = cu[b + 1] - cu[b];
   int instr = instr_len ? instr_len[b] : 0;
   instr = instr < len ? instr : len;
-  int s0 = instr, s1 = len;
-  float den = (float)(len - instr);
-  if (mode == GRIT_POOL_WEIGHTEDMEAN) { const float n = (float)(len - instr); den = 0.5f * n * (n + 1.f); }
-  if (mode == GRIT_POOL_CLS) { s0 = 0; s1 = len > 0 ? 1 : 0; den = 1.f; }
-  if (mode == GRIT_POOL_LASTTOKEN) { s0 = len > 0 ? len - 1 : 0; s1 = len; den = 1.f; }
+  const PackedSpan p = packed_span(len, instr, mode);
   const bool ramp = (mode == GRIT_POOL_WEIGHTEDMEAN);
-  const int HC = H >> 3;
-  const uint4* hb = reinterpret_cast<const uint4*>(hidden) + start * HC;
-  float* ob = out + (int64_t)b * H;
-  float ssq = 0.f;
-  for (int cc = tid; cc < HC; cc += POOL_THREADS) {
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int s = s0;
-    for (; s + 8 <= s1; s += 8) {  // 8 row loads in flight per lane (see pool_norm_fwd_k)
-      uint4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = hb[(int64_t)(s + u) * HC + cc];
-      const float w0 = ramp ? (float)(s - instr + 1) : 1.f;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) fma8(a, v[u], ramp ? w0 + (float)u : 1.f);
-    }
-    for (; s + 4 <= s1; s += 4) {
-      const uint4 v0 = hb[(int64_t)s * HC + cc], v1 = hb[(int64_t)(s + 1) * HC + cc];
-      const uint4 v2 = hb[(int64_t)(s + 2) * HC + cc], v3 = hb[(int64_t)(s + 3) * HC + cc];
-      const float w0 = ramp ? (float)(s - instr + 1) : 1.f;
-      fma8(a, v0, w0); fma8(a, v1, ramp ? w0 + 1.f : 1.f); fma8(a, v2, ramp ? w0 + 2.f : 1.f); fma8(a, v3, ramp ? w0 + 3.f : 1.f);
-    }
-    for (; s < s1; ++s) fma8(a, hb[(int64_t)s * HC + cc], ramp ? (float)(s - instr + 1) : 1.f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { a[e] = a[e] / den; ssq += a[e] * a[e]; }
-    float4* o4 = reinterpret_cast<float4*>(ob + cc * 8);
-    o4[0] = make_float4(a[0], a[1], a[2], a[3]);
-    o4[1] = make_float4(a[4], a[5], a[6], a[7]);
-  }
-  if (!normalize) {
-    if (inv_norm && tid == 0) inv_norm[b] = 1.f;
-    return;
-  }
-  ssq = wave_sum(ssq);
-  if (lane == 0) red[wave] = ssq;
+  pool_reduce_normalize(reinterpret_cast<const uint4*>(hidden) + start * (H >> 3), H, p.s0, p.s1, [](int s) { return s; },
+                        [ramp, instr](int s) { return ramp ? (float)(s - instr + 1) : 1.f; }, p.den, out + (int64_t)b * H,
+                        inv_norm ? inv_norm + b : nullptr, normalize, red);
+}
+
+// Backward, both layouts: g[0..H) (LDS) = (dy - y (y.dy)) * inv  (normalize)  or dy.  red: POOL_THREADS / 64 floats of LDS.  The
+// barrier inside also publishes what the caller wrote to LDS before the call; the caller adds the barrier that publishes g.
+__device__ __forceinline__ void pool_bwd_g(const float* __restrict__ yb, const float* __restrict__ dyb, float inv, int H, int normalize,
+                                           float* g, float* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float dot = 0.f;
+  if (normalize)
+    for (int i = tid; i < H; i += POOL_THREADS) dot += yb[i] * dyb[i];
+  dot = wave_sum(dot);
+  if (lane == 0) red[wave] = dot;
   __syncthreads();
   float tot = 0.f;
 #pragma unroll
   for (int w = 0; w < POOL_THREADS / 64; ++w) tot += red[w];
-  const float inv = 1.0f / fmaxf(sqrtf(tot), 1e-12f);
-  if (inv_norm && tid == 0) inv_norm[b] = inv;
-  for (int cc = tid; cc < HC; cc += POOL_THREADS) {
-    float4* o4 = reinterpret_cast<float4*>(ob + cc * 8);
-    float4 x = o4[0], y = o4[1];
-    x.x *= inv; x.y *= inv; x.z *= inv; x.w *= inv; y.x *= inv; y.y *= inv; y.z *= inv; y.w *= inv;
-    o4[0] = x; o4[1] = y;
+  for (int i = tid; i < H; i += POOL_THREADS) g[i] = normalize ? (dyb[i] - yb[i] * tot) * inv : dyb[i];
+}
+
+// one wave writes one row of dhidden: w * g, or zeros where the row has no pooling weight
+__device__ __forceinline__ void pool_bwd_write_row(uint4* __restrict__ drow, const float* g, int HC, float w) {
+  for (int cc = threadIdx.x & 63; cc < HC; cc += 64) {
+    uint4 o = make_uint4(0, 0, 0, 0);
+    if (w != 0.f) {
+      const float4 g0 = *reinterpret_cast<const float4*>(g + cc * 8), g1 = *reinterpret_cast<const float4*>(g + cc * 8 + 4);
+      o.x = pack2bf(w * g0.x, w * g0.y); o.y = pack2bf(w * g0.z, w * g0.w);
+      o.z = pack2bf(w * g1.x, w * g1.y); o.w = pack2bf(w * g1.z, w * g1.w);
+    }
+    drow[cc] = o;
   }
 }
 
@@ -216,40 +220,17 @@ __global__ void __launch_bounds__(POOL_THREADS) pool_norm_bwd_k(const float* __r
   int* nzp = reinterpret_cast<int*>(red + 8);
   float* denp = red + 9;
 
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
   if (wave == 0) pool_weights(mask + (int64_t)b * S, instr_len ? instr_len[b] : 0, S, mode, cs, cw, nzp, denp);
   for (int s = tid; s < S; s += POOL_THREADS) ws[s] = 0.f;
-  const float* yb = y + (int64_t)b * H;
-  const float* dyb = dy + (int64_t)b * H;
-  float dot = 0.f;
-  if (normalize)
-    for (int i = tid; i < H; i += POOL_THREADS) dot += yb[i] * dyb[i];
-  dot = wave_sum(dot);
-  if (lane == 0) red[wave] = dot;
-  __syncthreads();
-  float tot = 0.f;
-#pragma unroll
-  for (int w = 0; w < POOL_THREADS / 64; ++w) tot += red[w];
-  const float inv = normalize ? inv_norm[b] : 1.f;
-  for (int i = tid; i < H; i += POOL_THREADS) g[i] = normalize ? (dyb[i] - yb[i] * tot) * inv : dyb[i];
+  pool_bwd_g(y + (int64_t)b * H, dy + (int64_t)b * H, normalize ? inv_norm[b] : 1.f, H, normalize, g, red);
   const int nz = *nzp;
   const float inv_den = 1.0f / *denp;
   for (int k = tid; k < nz; k += POOL_THREADS) ws[cs[k]] = cw[k] * inv_den;
   __syncthreads();
   const int HC = H >> 3;
   uint4* db = reinterpret_cast<uint4*>(dhidden + (int64_t)b * S * H);
-  for (int s = wave; s < S; s += POOL_THREADS / 64) {
-    const float w = ws[s];
-    for (int cc = lane; cc < HC; cc += 64) {
-      uint4 o = make_uint4(0, 0, 0, 0);
-      if (w != 0.f) {
-        const float4 g0 = *reinterpret_cast<const float4*>(g + cc * 8), g1 = *reinterpret_cast<const float4*>(g + cc * 8 + 4);
-        o.x = pack2bf(w * g0.x, w * g0.y); o.y = pack2bf(w * g0.z, w * g0.w);
-        o.z = pack2bf(w * g1.x, w * g1.y); o.w = pack2bf(w * g1.z, w * g1.w);
-      }
-      db[(int64_t)s * HC + cc] = o;
-    }
-  }
+  for (int s = wave; s < S; s += POOL_THREADS / 64) pool_bwd_write_row(db + (int64_t)s * HC, g, HC, ws[s]);
 }
 
 // packed rows: dhidden[cu[b]+s, :] = w(s) * g with the weights of pool_norm_varlen_fwd_k (no mask: every packed row is a token)
@@ -260,46 +241,22 @@ __global__ void __launch_bounds__(POOL_THREADS) pool_norm_varlen_bwd_k(const flo
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* g = reinterpret_cast<float*>(smem);  // [H]
   float* red = g + H;                         // [POOL_THREADS/64]
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, wave = threadIdx.x >> 6;
   const int64_t start = cu[b];
   const int len = cu[b + 1] - cu[b];
   int instr = instr_len ? instr_len[b] : 0;
   instr = instr < len ? instr : len;
-  int s0 = instr, s1 = len;
-  float den = (float)(len - instr);
-  if (mode == GRIT_POOL_WEIGHTEDMEAN) { const float n = (float)(len - instr); den = 0.5f * n * (n + 1.f); }
-  if (mode == GRIT_POOL_CLS) { s0 = 0; s1 = len > 0 ? 1 : 0; den = 1.f; }
-  if (mode == GRIT_POOL_LASTTOKEN) { s0 = len > 0 ? len - 1 : 0; s1 = len; den = 1.f; }
+  const PackedSpan p = packed_span(len, instr, mode);
   const bool ramp = (mode == GRIT_POOL_WEIGHTEDMEAN);
-  const float* yb = y + (int64_t)b * H;
-  const float* dyb = dy + (int64_t)b * H;
-  float dot = 0.f;
-  if (normalize)
-    for (int i = tid; i < H; i += POOL_THREADS) dot += yb[i] * dyb[i];
-  dot = wave_sum(dot);
-  if (lane == 0) red[wave] = dot;
+  pool_bwd_g(y + (int64_t)b * H, dy + (int64_t)b * H, normalize ? inv_norm[b] : 1.f, H, normalize, g, red);
   __syncthreads();
-  float tot = 0.f;
-#pragma unroll
-  for (int w = 0; w < POOL_THREADS / 64; ++w) tot += red[w];
-  const float inv = normalize ? inv_norm[b] : 1.f;
-  for (int i = tid; i < H; i += POOL_THREADS) g[i] = normalize ? (dyb[i] - yb[i] * tot) * inv : dyb[i];
-  __syncthreads();
-  const float inv_den = 1.0f / den;
+  const float inv_den = 1.0f / p.den;
   const int HC = H >> 3;
   uint4* db = reinterpret_cast<uint4*>(dhidden) + start * HC;
   for (int s = wave; s < len; s += POOL_THREADS / 64) {
     float w = 0.f;
-    if (s >= s0 && s < s1) w = (ramp ? (float)(s - instr + 1) : 1.f) * inv_den;
-    for (int cc = lane; cc < HC; cc += 64) {
-      uint4 o = make_uint4(0, 0, 0, 0);
-      if (w != 0.f) {
-        const float4 g0 = *reinterpret_cast<const float4*>(g + cc * 8), g1 = *reinterpret_cast<const float4*>(g + cc * 8 + 4);
-        o.x = pack2bf(w * g0.x, w * g0.y); o.y = pack2bf(w * g0.z, w * g0.w);
-        o.z = pack2bf(w * g1.x, w * g1.y); o.w = pack2bf(w * g1.z, w * g1.w);
-      }
-      db[(int64_t)s * HC + cc] = o;
-    }
+    if (s >= p.s0 && s < p.s1) w = (ramp ? (float)(s - instr + 1) : 1.f) * inv_den;
+    pool_bwd_write_row(db + (int64_t)s * HC, g, HC, w);
   }
 }
 
@@ -307,17 +264,16 @@ __global__ void __launch_bounds__(POOL_THREADS) pool_norm_varlen_bwd_k(const flo
 
 using namespace grit;
 
-// A dynamic-LDS opt-in is a PER-DEVICE function attribute: set once per (kernel, device), from whichever thread gets there first
-// (autograd worker threads call into the backward entry points concurrently).
-template <typename KernelT>
-static void lds_optin_once(KernelT kernel, std::atomic<uint64_t>& done, int bytes) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done.fetch_or(bit, std::memory_order_release);
-  }
+// The argument checks that the four entry points share, in the caller's name (S = 1 for the packed layouts, inv_ok = true for the forward;
+// h_max > 0: H is bounded by the LDS row of the packed backward).  The checks that only one entry point has follow it there.
+static int pool_check(const char* fn, bool ptrs_ok, bool inv_ok, int B, int S, int H, int mode, int h_max) {
+  GRIT_REQUIRE(ptrs_ok, GRIT_E_BADARG, "%s: null pointer", fn);
+  GRIT_REQUIRE(inv_ok, GRIT_E_BADARG, "%s: inv_norm required when normalize", fn);
+  GRIT_REQUIRE(B >= 0 && S > 0 && H > 0, GRIT_E_BADARG, "%s: bad sizes", fn);
+  GRIT_REQUIRE(mode >= GRIT_POOL_MEAN && mode <= GRIT_POOL_LASTTOKEN, GRIT_E_BADARG, "%s: unknown pooling mode %d", fn, mode);
+  if (h_max > 0) GRIT_REQUIRE(H % 8 == 0 && H <= h_max, GRIT_E_UNSUPPORTED, "%s: H=%d must be a multiple of 8, <= %d", fn, H, h_max);
+  else GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "%s: H=%d must be a multiple of 8", fn, H);
+  return GRIT_OK;
 }
 
 extern "C" {
@@ -325,16 +281,11 @@ extern "C" {
 int grit_pool_norm_fwd(const void* hidden, const int64_t* mask, const int32_t* instr_len, float* out, float* inv_norm, int B, int S,
                        int H, int mode, int normalize, void* stream) {
   if (B == 0) return GRIT_OK;
-  GRIT_REQUIRE(hidden && mask && out, GRIT_E_BADARG, "grit_pool_norm_fwd: null pointer");
-  GRIT_REQUIRE(B >= 0 && S > 0 && H > 0, GRIT_E_BADARG, "grit_pool_norm_fwd: bad sizes");
-  GRIT_REQUIRE(mode >= GRIT_POOL_MEAN && mode <= GRIT_POOL_LASTTOKEN, GRIT_E_BADARG, "grit_pool_norm_fwd: unknown pooling mode %d", mode);
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_pool_norm_fwd: H=%d must be a multiple of 8", H);
+  if (const int rc = pool_check("grit_pool_norm_fwd", hidden && mask && out, true, B, S, H, mode, 0)) return rc;
   GRIT_REQUIRE(S <= 16384, GRIT_E_UNSUPPORTED, "grit_pool_norm_fwd: S=%d > 16384", S);
   GRIT_REQUIRE(aligned16(hidden) && aligned16(out), GRIT_E_BADARG, "grit_pool_norm_fwd: pointers must be 16-byte aligned");
-  if (B == 0) return GRIT_OK;
   const size_t lds = 8 * (size_t)S + 64;
-  static std::atomic<uint64_t> optin_f{0};
-  lds_optin_once(pool_norm_fwd_k, optin_f, 160 * 1024);
+  lds_optin_once<pool_norm_fwd_k>(160 * 1024);
   hipLaunchKernelGGL(pool_norm_fwd_k, dim3(B), dim3(POOL_THREADS), lds, (hipStream_t)stream, (const uint16_t*)hidden, mask, instr_len,
                      out, inv_norm, S, H, mode, normalize);
   GRIT_CHECK_LAUNCH("grit_pool_norm_fwd");
@@ -344,12 +295,8 @@ int grit_pool_norm_fwd(const void* hidden, const int64_t* mask, const int32_t* i
 int grit_pool_norm_varlen_fwd(const void* hidden, const int32_t* cu_seqlens, const int32_t* instr_len, float* out, float* inv_norm, int B,
                               int H, int mode, int normalize, void* stream) {
   if (B == 0) return GRIT_OK;
-  GRIT_REQUIRE(hidden && cu_seqlens && out, GRIT_E_BADARG, "grit_pool_norm_varlen_fwd: null pointer");
-  GRIT_REQUIRE(B >= 0 && H > 0, GRIT_E_BADARG, "grit_pool_norm_varlen_fwd: bad sizes");
-  GRIT_REQUIRE(mode >= GRIT_POOL_MEAN && mode <= GRIT_POOL_LASTTOKEN, GRIT_E_BADARG, "grit_pool_norm_varlen_fwd: unknown pooling mode %d", mode);
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_pool_norm_varlen_fwd: H=%d must be a multiple of 8", H);
+  if (const int rc = pool_check("grit_pool_norm_varlen_fwd", hidden && cu_seqlens && out, true, B, 1, H, mode, 0)) return rc;
   GRIT_REQUIRE(aligned16(hidden) && aligned16(out), GRIT_E_BADARG, "grit_pool_norm_varlen_fwd: pointers must be 16-byte aligned");
-  if (B == 0) return GRIT_OK;
   hipLaunchKernelGGL(pool_norm_varlen_fwd_k, dim3(B), dim3(POOL_THREADS), 0, (hipStream_t)stream, (const uint16_t*)hidden, cu_seqlens,
                      instr_len, out, inv_norm, H, mode, normalize);
   GRIT_CHECK_LAUNCH("grit_pool_norm_varlen_fwd");
@@ -358,17 +305,12 @@ int grit_pool_norm_varlen_fwd(const void* hidden, const int32_t* cu_seqlens, con
 
 int grit_pool_norm_bwd(const float* y, const float* dy, const float* inv_norm, const int64_t* mask, const int32_t* instr_len,
                        void* dhidden, int B, int S, int H, int mode, int normalize, void* stream) {
-  GRIT_REQUIRE(y && dy && mask && dhidden, GRIT_E_BADARG, "grit_pool_norm_bwd: null pointer");
-  GRIT_REQUIRE(!normalize || inv_norm, GRIT_E_BADARG, "grit_pool_norm_bwd: inv_norm required when normalize");
-  GRIT_REQUIRE(B >= 0 && S > 0 && H > 0, GRIT_E_BADARG, "grit_pool_norm_bwd: bad sizes");
-  GRIT_REQUIRE(mode >= GRIT_POOL_MEAN && mode <= GRIT_POOL_LASTTOKEN, GRIT_E_BADARG, "grit_pool_norm_bwd: unknown pooling mode %d", mode);
-  GRIT_REQUIRE(H % 8 == 0, GRIT_E_UNSUPPORTED, "grit_pool_norm_bwd: H=%d must be a multiple of 8", H);
+  if (const int rc = pool_check("grit_pool_norm_bwd", y && dy && mask && dhidden, !normalize || inv_norm, B, S, H, mode, 0)) return rc;
   const size_t lds = 4 * (size_t)H + 12 * (size_t)S + 64;
   GRIT_REQUIRE(lds <= 160 * 1024, GRIT_E_UNSUPPORTED, "grit_pool_norm_bwd: H=%d S=%d exceed LDS", H, S);
   GRIT_REQUIRE(aligned16(dhidden), GRIT_E_BADARG, "grit_pool_norm_bwd: pointers must be 16-byte aligned");
   if (B == 0) return GRIT_OK;
-  static std::atomic<uint64_t> optin_b{0};
-  lds_optin_once(pool_norm_bwd_k, optin_b, 160 * 1024);
+  lds_optin_once<pool_norm_bwd_k>(160 * 1024);
   hipLaunchKernelGGL(pool_norm_bwd_k, dim3(B), dim3(POOL_THREADS), lds, (hipStream_t)stream, y, dy, inv_norm, mask, instr_len,
                      (uint16_t*)dhidden, S, H, mode, normalize);
   GRIT_CHECK_LAUNCH("grit_pool_norm_bwd");
@@ -378,15 +320,11 @@ int grit_pool_norm_bwd(const float* y, const float* dy, const float* inv_norm, c
 int grit_pool_norm_varlen_bwd(const float* y, const float* dy, const float* inv_norm, const int32_t* cu_seqlens, const int32_t* instr_len,
                               void* dhidden, int B, int H, int mode, int normalize, void* stream) {
   if (B == 0) return GRIT_OK;
-  GRIT_REQUIRE(y && dy && cu_seqlens && dhidden, GRIT_E_BADARG, "grit_pool_norm_varlen_bwd: null pointer");
-  GRIT_REQUIRE(!normalize || inv_norm, GRIT_E_BADARG, "grit_pool_norm_varlen_bwd: inv_norm required when normalize");
-  GRIT_REQUIRE(B >= 0 && H > 0, GRIT_E_BADARG, "grit_pool_norm_varlen_bwd: bad sizes");
-  GRIT_REQUIRE(mode >= GRIT_POOL_MEAN && mode <= GRIT_POOL_LASTTOKEN, GRIT_E_BADARG, "grit_pool_norm_varlen_bwd: unknown pooling mode %d", mode);
-  GRIT_REQUIRE(H % 8 == 0 && H <= 32768, GRIT_E_UNSUPPORTED, "grit_pool_norm_varlen_bwd: H=%d must be a multiple of 8, <= 32768", H);
+  if (const int rc = pool_check("grit_pool_norm_varlen_bwd", y && dy && cu_seqlens && dhidden, !normalize || inv_norm, B, 1, H, mode, 32768))
+    return rc;
   GRIT_REQUIRE(aligned16(dhidden), GRIT_E_BADARG, "grit_pool_norm_varlen_bwd: pointers must be 16-byte aligned");
   const size_t lds = 4 * (size_t)H + 64;
-  static std::atomic<uint64_t> optin_vb{0};
-  lds_optin_once(pool_norm_varlen_bwd_k, optin_vb, 160 * 1024);
+  lds_optin_once<pool_norm_varlen_bwd_k>(160 * 1024);
   hipLaunchKernelGGL(pool_norm_varlen_bwd_k, dim3(B), dim3(POOL_THREADS), lds, (hipStream_t)stream, y, dy, inv_norm, cu_seqlens, instr_len,
                      (uint16_t*)dhidden, H, mode, normalize);
   GRIT_CHECK_LAUNCH("grit_pool_norm_varlen_bwd");

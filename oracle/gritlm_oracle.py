@@ -465,8 +465,9 @@ def pool_normalize_backward(hidden, pool_mask, method, normalized, grad_out):
     elif method == "cls":
         m = np.zeros_like(m); m[:, 0] = 1
     elif method == "lasttoken":
-        left = bool(pool_mask[:, -1].sum() == pool_mask.shape[0])
-        idx = np.full((m.shape[0],), m.shape[1] - 1) if left else pool_mask.sum(axis=1) - 1
+        # the position pooling() reads: the last one with a non-zero mask (== mask.sum - 1 on a right-padded row without instruction
+        # tokens, == the last position on a left-padded batch, :190-207)
+        idx = np.clip(m.shape[1] - np.argmax(pool_mask[:, ::-1], axis=1) - 1, 0, None)
         m = np.zeros_like(m); m[np.arange(m.shape[0]), idx] = 1
     den = m.sum(axis=1, keepdims=True).astype(F64)
     w = m / den

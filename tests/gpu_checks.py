@@ -4439,6 +4439,9 @@ ALL_CHECKS = [
     ("rmsnorm_4096", check_rmsnorm, dict(T=37, H=4096)),
     ("rmsnorm_256", check_rmsnorm, dict(T=9, H=256)),
     ("rmsnorm_1024", check_rmsnorm, dict(T=130, H=1024)),
+    ("rmsnorm_4096_few_rows", check_rmsnorm, dict(T=3, H=4096)),            # T <= 16: the form that prefetches the weight row
+    ("rmsnorm_2048", check_rmsnorm, dict(T=37, H=2048)),
+    ("rmsnorm_8192", check_rmsnorm, dict(T=37, H=8192)),
     ("rope", check_rope, {}),
     ("rope_inv", check_rope, dict(inverse=True)),
     ("gemm_256", check_gemm, dict(M=256, N=256, K=64)),
@@ -4454,6 +4457,8 @@ ALL_CHECKS = [
     ("f32_stream_ops", check_f32_stream_ops, {}),
     ("f32_stream_ops_768", check_f32_stream_ops, dict(T=9, H=768)),
     ("f32_stream_ops_264", check_f32_stream_ops, dict(T=5, H=264)),
+    ("f32_stream_ops_2048", check_f32_stream_ops, dict(T=37, H=2048)),
+    ("f32_stream_ops_8192", check_f32_stream_ops, dict(T=37, H=8192)),
     ("gemm_counter_rings_reclaimed", check_gemm_counter_rings_are_reclaimed, {}),
     ("gemm_pair", check_gemm_pair, {}),
     ("gemm_pair_store", check_gemm_pair, dict(M1=17, N1=1536, M2=1024, N2=256, K=256, accumulate=False)),
@@ -4480,10 +4485,14 @@ ALL_CHECKS = [
     ("pool_weightedmean", check_pool, dict(method="weightedmean")),
     ("pool_cls", check_pool, dict(method="cls")),
     ("pool_lasttoken", check_pool, dict(method="lasttoken")),
+    ("pool_cls_4096", check_pool, dict(method="cls", B=2, S=19, H=4096)),
+    ("pool_lasttoken_4096", check_pool, dict(method="lasttoken", B=2, S=19, H=4096)),
     ("pool_mean_nonorm", check_pool, dict(method="mean", normalize=False)),
     ("pool_mean_4096", check_pool, dict(method="mean", B=2, S=19, H=4096)),
     ("pool_bwd_mean", check_pool_bwd, dict(method="mean")),
     ("pool_bwd_weightedmean", check_pool_bwd, dict(method="weightedmean")),
+    ("pool_bwd_cls", check_pool_bwd, dict(method="cls")),
+    ("pool_bwd_lasttoken", check_pool_bwd, dict(method="lasttoken")),
     ("pool_bwd_nonorm", check_pool_bwd, dict(method="mean", normalize=False)),
     ("infonce_a", check_infonce, dict(tag="a")),
     ("infonce_b", check_infonce, dict(tag="b")),
@@ -4527,6 +4536,7 @@ ALL_CHECKS = [
     ("attn_bwd_varlen_gqa4", check_attention_bwd_varlen, dict(lens=(129, 64, 257), nq=8, nkv=2)),
     ("pool_bwd_varlen_mean", check_pool_bwd_varlen, dict(method="mean")),
     ("pool_bwd_varlen_weightedmean", check_pool_bwd_varlen, dict(method="weightedmean")),
+    ("pool_bwd_varlen_cls", check_pool_bwd_varlen, dict(method="cls")),
     ("pool_bwd_varlen_lasttoken", check_pool_bwd_varlen, dict(method="lasttoken", normalize=False)),
     ("embed_scatter", check_embed_scatter, {}),
     ("encoder_tiny", check_encoder_golden, dict(cfg_name="tiny")),
@@ -4565,8 +4575,12 @@ ALL_CHECKS = [
     ("f16_overflow_flag", check_f16_overflow_flag, {}),
     ("f16_stream_ops", check_f16_stream_ops, {}),
     ("f16_stream_ops_264", check_f16_stream_ops, dict(T=5, H=264)),
+    ("f16_stream_ops_2048", check_f16_stream_ops, dict(T=37, H=2048)),
+    ("f16_stream_ops_8192", check_f16_stream_ops, dict(T=37, H=8192)),
     ("f16_stream_norm_and_gather", check_f16_stream_norm_and_gather, {}),
     ("f16_stream_norm_and_gather_264", check_f16_stream_norm_and_gather, dict(T=5, H=264)),
+    ("f16_stream_norm_and_gather_2048", check_f16_stream_norm_and_gather, dict(T=37, H=2048)),
+    ("f16_stream_norm_and_gather_8192", check_f16_stream_norm_and_gather, dict(T=37, H=8192)),
     ("attn_f16_ragged", check_attention_f16, dict(mask_kind="ragged")),
     ("attn_f16_holes", check_attention_f16, dict(mask_kind="holes", S=257)),
     ("attn_f16_full_512", check_attention_f16, dict(B=1, S=512, nq=8, nkv=2, mask_kind="none")),

@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Per-kernel timings at GritLM-7B shapes (HIP events on torch's current stream). Prints TF/s and GB/s."""
+"""Per-kernel timings at GritLM-7B shapes (HIP events on torch's current stream). Prints TF/s and GB/s.
+`gpu_microbench.py rows` times the HBM-bound row kernels alone and ends with one JSON line {case: median ms} for A/B runs
+(GRIT_HIP_LIB picks the library; one fresh process per run)."""
+import json
 import os
 import sys
 
@@ -107,7 +110,61 @@ def new_kernel_cases():
         print(f"gemv {tag:<8s} N={N:<6d} K={K:<6d}  med {med * 1e3:7.1f} us  {N * K * 2 / med / 1e6:8.1f} GB/s", flush=True)
 
 
+def row_kernel_cases(T=131072, H=4096, B=256, S=512, E=8):
+    """The row kernels of csrc/elementwise.hip, pool.hip and moe.hip at the encoder's shapes: median ms per call, 30 timed calls each."""
+    F16, F32 = torch.float16, torch.float32
+    res = {}
+
+    def case(name, fn, gbytes, iters=30, per=1):
+        med, _ = timeit(fn, iters=iters)
+        res[name] = med / per
+        print(f"{name:<44s} med {med / per * 1e3:10.2f} us  {gbytes / (med / per) / 1e6:8.1f} GB/s", flush=True)
+
+    xf = torch.randn((T, H), device=DEV, dtype=F32)
+    w = (1 + 0.1 * torch.randn((H,), device=DEV)).to(BF)
+    for tag, din, dout in (("bf16_bf16", BF, BF), ("f32_bf16", F32, BF), ("f32_f16", F32, F16), ("f16_f16", F16, F16), ("f16_bf16", F16, BF)):
+        x, y = xf.to(din), torch.empty((T, H), device=DEV, dtype=dout)
+        case(f"rmsnorm {tag} T={T} H={H}", lambda: ops.rmsnorm(x, w, 1e-5, out=y), T * H * (x.element_size() + 2))
+        del x, y
+    x1, y1 = xf[:1].to(BF), torch.empty((1, H), device=DEV, dtype=BF)
+
+    def one_row_x1000():
+        for _ in range(1000):
+            ops.rmsnorm(x1, w, 1e-5, out=y1)
+    case(f"rmsnorm bf16_bf16 T=1 H={H} (per launch of 1000)", one_row_x1000, 4 * H, iters=10, per=1000)   # launch-bound
+    ids = torch.randint(0, 32000, (T,), device=DEV)
+    tab = torch.randn((32000, H), device=DEV, dtype=F32).to(BF)
+    for tag, dout in (("bf16", BF), ("f32", F32)):
+        y = torch.empty((T, H), device=DEV, dtype=dout)
+        case(f"embed_gather {tag} T={T} H={H}", lambda: ops.embed_gather(tab, ids, out=y), T * H * (2 + y.element_size()))
+        del y
+    del tab
+    xb = xf.to(BF)
+    mask = torch.ones((B, S), dtype=torch.int64, device=DEV)
+    cu = (torch.arange(B + 1, device=DEV) * S).to(torch.int32)
+    dy = torch.randn((B, H), device=DEV, dtype=F32)
+    inv = torch.empty((B,), device=DEV, dtype=F32)
+    for mode in ("mean", "weightedmean"):
+        yp = ops.pool_norm(xb.view(B, S, H), mask, mode, True, inv_norm=inv)
+        case(f"pool fwd padded {mode} {B}x{S}x{H}", lambda: ops.pool_norm(xb.view(B, S, H), mask, mode, True), T * H * 2)
+        case(f"pool fwd packed {mode} {B}x{S}x{H}", lambda: ops.pool_norm_varlen(xb, cu, mode, True), T * H * 2)
+        case(f"pool bwd padded {mode} {B}x{S}x{H}", lambda: ops.pool_norm_bwd(yp, dy, inv, mask, mode, True, S), T * H * 2)
+        case(f"pool bwd packed {mode} {B}x{S}x{H}", lambda: ops.pool_norm_varlen_bwd(yp, dy, inv, cu, T, mode, True), T * H * 2)
+    gw = (torch.randn((E, H), device=DEV) * 0.5).to(BF)
+    case(f"moe router+index bf16 T={T} E={E}", lambda: ops.moe_route(xb, gw), T * H * 2)
+    case(f"moe router+index f32 T={T} E={E}", lambda: ops.moe_route_f32(xf, w, 1e-5, gw), T * H * 4)
+    _, wts, _, _, rows = ops.moe_route(xb, gw)
+    del xf
+    yy = torch.randn((2 * T, H), device=DEV, dtype=F32).to(BF)
+    out = torch.empty_like(xb)
+    case(f"moe combine T={T}", lambda: ops.moe_combine(yy, rows, wts, xb, out=out), 4 * T * H * 2)
+    print(json.dumps({"lib": os.environ.get("GRIT_HIP_LIB", "tree"), "median_ms": res}), flush=True)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "rows":
+        row_kernel_cases()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "new":
         new_kernel_cases()
         sys.exit(0)

@@ -28,8 +28,8 @@ for line in r.stderr.splitlines():
         k, v = t.split(":", 1)
         cur[k.strip()] = v.strip()
 for c in rows:
-    name = subprocess.run(["c++filt", c["name"]], capture_output=True, text=True).stdout.strip()
-    name = re.sub(r"\(.*", "", name).replace("void ", "")
+    name = subprocess.run(["c++filt", "-p", c["name"]], capture_output=True, text=True).stdout.strip()
+    name = name.replace("void ", "").replace("grit::RowFmt", "RowFmt")
     if flt and flt not in name:
         continue
     print(f"{name:48s} VGPR {c.get('VGPRs','?'):>4s} AGPR {c.get('AGPRs','?'):>4s} SGPR {c.get('SGPRs','?'):>4s} spillV {c.get('VGPRs Spill','?'):>3s} "
