@@ -52,20 +52,11 @@ attn_bidir_fwd_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ 
   typedef typename att_frag<F16>::type frag_t;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware decode: the k-th workgroup of XCD x belongs to K/V set (k / U) * 8 + x, U = (heads per kv head) x (query-block groups)
-  const int gqa = nq / nkv, U = gqa * ngx;
-  const int kx = (int)blockIdx.x >> 3;
-  const int set = (kx / U) * 8 + ((int)blockIdx.x & 7), member = kx % U;
-  if (set >= n_sets) return;
-  const int b = set / nkv, hk = set - b * nkv;
+  const int gqa = nq / nkv;
+  ATT_WG_DECODE(gqa * ngx, member)                // U = (heads per kv head) x (query-block groups)
   const int h = hk * gqa + member % gqa;
   const int qb_first = (member / gqa) * qpw;
-  int S = S_arg;
-  int64_t row0 = (int64_t)b * S_arg;
-  if constexpr (VARLEN) {
-    row0 = cu_seqlens[b];
-    S = cu_seqlens[b + 1] - cu_seqlens[b];
-  }
+  ATT_SEQ_BOUNDS()
   if (qb_first * ATT_QB >= S) return;            // uniform per workgroup
 #ifdef ATT_TIMING
   const uint64_t att_t0 = __builtin_readcyclecounter();

@@ -16,37 +16,18 @@
 // As in the forward every product is arranged so that the owned index is the MFMA "column" (lane&31): the softmax
 // statistics are lane-local (dq kernel) or a broadcast LDS read (dkdv kernel), and P / dS feed the next MFMA from
 // registers with the contraction-index permutation applied on the transposed-LDS-image side.
-#include <atomic>
-
-#include "common.h"
+#include "attn_tile.h"
 
 namespace grit {
 
-constexpr int AB_D = 128;
 constexpr int AB_IMG = 64 * 256;              // one staged tile: row-major [64 rows][256 B]
 constexpr int AB_STAGE = 2 * AB_IMG;          // two images per ring stage (Q + dO, or K + V)
 constexpr int AB_RING = 2 * AB_STAGE;         // 64 KiB
-typedef const __attribute__((address_space(1))) void* ab_gptr_t;
-typedef __attribute__((address_space(3))) void* ab_lptr_t;
-typedef __attribute__((ext_vector_type(4))) short ab_s16x4_t;
 
-// s_waitcnt through the builtin (gfx9 encoding) so that the waitcnt insertion pass sees it (cf. attention.hip)
-#define AB_WAIT_VM0()                       \
-  do {                                      \
-    asm volatile("" ::: "memory");          \
-    __builtin_amdgcn_s_waitcnt(0x0F70);     \
-    asm volatile("" ::: "memory");          \
-  } while (0)
 #define AB_SCHED_FENCE()                    \
   do {                                      \
     asm volatile("" ::: "memory");          \
     __builtin_amdgcn_sched_barrier(0);      \
-  } while (0)
-#define AB_WAIT_LGKM0()                     \
-  do {                                      \
-    asm volatile("" ::: "memory");          \
-    __builtin_amdgcn_s_waitcnt(0xC07F);     \
-    asm volatile("" ::: "memory");          \
   } while (0)
 
 // Every staged image is read BOTH as row fragments (ds_read_b128: 16 rows x one 16-byte unit per lane group) and through the
@@ -55,16 +36,31 @@ typedef __attribute__((ext_vector_type(4))) short ab_s16x4_t;
 // -- a bijection of row & 15 (conflict-free row fragments) whose bits 3:2 enumerate 4 consecutive rows (conflict-free transposing
 // reads).  The image of an LDS-DMA is lane-linear, so the swizzle goes into the per-lane SOURCE address.
 //
-// Stage rows r0 .. r0+63 (clamped to < limit) of a [rows][stride] bf16 matrix, 128 columns from `base`: wave w fills rows 16w..16w+15
-// with four 1-KiB instructions (4 rows x 256 B each).
-__device__ __forceinline__ void stage_img(const char* base, uint32_t stride_b, int r0, int limit, char* img, int wv, int lane) {
+// Stage this wave's 16 rows of a tile into the TWO images of a ring stage (sb: the wave's 4 KiB of image 0; image 1 sits AB_IMG behind):
+// four 1-KiB instructions (4 rows x 256 B each) per image.  Buffer-addressed LDS-DMA (round 6, as the forward kernel): the descriptor's
+// range check zero-fills rows past the sequence -- no per-tile clamp / 64-bit multiply per piece.  The lane's offset of piece i is
+// [(lane>>4) rows + the swizzled unit of piece 0, g(16w + (lane>>4)) << 4] ^ (i << 4): the strides are multiples of 256 B, so the unit
+// sits alone in bits 7:4 and g(row) of piece i differs from piece 0's in bits 5:4 only -- one v_xor per piece from values that are
+// recomputed from a laundered lane id in every call (kept across the tile loop they are the first registers hipcc spills, and a
+// scratch reload's vmcnt wait would sit between the DMA pieces); the piece's 4 i rows, the wave's 16 rows, the tile and the head go
+// into the scalar offsets off0 / off1.  (Not a template over the descriptor type: hipcc then emits the host stub of the first kernel
+// instantiation only.)
+__device__ __forceinline__ void stage_pair(__amdgpu_buffer_rsrc_t r0, __amdgpu_buffer_rsrc_t r1, uint32_t stride0_b, uint32_t stride1_b,
+                                           uint32_t off0, uint32_t off1, char* sb, int lane) {
+  int ln = lane;
+  asm volatile("" : "+v"(ln));
+  const uint32_t u0_b = (uint32_t)(((ln & 15) ^ (((ln >> 4) & 3) << 2)) << 4);
+  const uint32_t x0 = (uint32_t)(ln >> 4) * stride0_b + u0_b, x1 = (uint32_t)(ln >> 4) * stride1_b + u0_b;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    int row = r0 + 16 * wv + 4 * i + (lane >> 4);
-    row = row < limit ? row : limit - 1;
-    const uint32_t unit = (uint32_t)((lane & 15) ^ ((((lane >> 4) & 3) << 2) | i));     // g(16w + 4i + (lane>>4))
-    __builtin_amdgcn_global_load_lds((ab_gptr_t)(base + ((uint32_t)row * stride_b + (unit << 4))), (ab_lptr_t)(img + (16 * wv + 4 * i) * 256), 16, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, (att_lptr_t)(sb + i * 1024), 16, (int)(x0 ^ (uint32_t)(i << 4)), (int)(off0 + 4u * i * stride0_b), 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, (att_lptr_t)(sb + AB_IMG + i * 1024), 16, (int)(x1 ^ (uint32_t)(i << 4)), (int)(off1 + 4u * i * stride1_b), 0, 0);
   }
+}
+// Index of the statistics (lse, delta) of query q of head h: padded layout [B, nq, S], packed layout [T, nq] (row0: the sequence's first
+// packed row)
+__device__ __forceinline__ int64_t stat_idx(bool varlen, int64_t row0, int64_t b, int h, int q, int nq, int S) {
+  return varlen ? (row0 + q) * nq + h : (b * nq + h) * S + q;
 }
 // A-operand fragment from the row-major image: A[row = rb*32 + (lane&31)][k = 16ks + 8hi + j]
 __device__ __forceinline__ bf16x8_t frag_rm(const char* img, int rb, int ks, int lane) {
@@ -87,8 +83,8 @@ __device__ __forceinline__ TrLane tr_lane(int lane) {
 }
 __device__ __forceinline__ bf16x8_t frag_tr(const char* img, int db, int rb, int c, const TrLane& t) {
   const char* p = img + (rb * 32 + c * 16) * 256;
-  const ab_s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ab_s16x4_t*)(p + (t.o0 ^ (db << 6))));
-  const ab_s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ab_s16x4_t*)(p + (t.o1 ^ (db << 6))));
+  const s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p + (t.o0 ^ (db << 6))));
+  const s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p + (t.o1 ^ (db << 6))));
   return __builtin_bit_cast(bf16x8_t, (__attribute__((ext_vector_type(8))) short){v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]});
 }
 // Store a wave's [32 rows][128] fp32 accumulator tile (MFMA "transposed" layout: lane (row = lane&31, hi) holds
@@ -112,7 +108,7 @@ __device__ __forceinline__ void store_tile_rows(const f32x16_t (&acc)[4], float 
       *reinterpret_cast<uint4*>(wp + (((db * 4 + gp * 2 + hi) ^ (ql & 15)) << 4)) =
           make_uint4(pack2bf_hw(a[0], a[1]), pack2bf_hw(a[2], a[3]), pack2bf_hw(bq[0], bq[1]), pack2bf_hw(bq[2], bq[3]));
     }
-  AB_WAIT_LGKM0();
+  ATT_WAIT_LGKM0();
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int r = 4 * j + (lane >> 4);
@@ -120,7 +116,7 @@ __device__ __forceinline__ void store_tile_rows(const f32x16_t (&acc)[4], float 
     if (row_first + r < limit)
       *reinterpret_cast<uint4*>(gbase + ((uint32_t)(row_first + r) * stride_b + (uint32_t)(((lane & 15) ^ (r & 15)) << 4))) = piece;
   }
-  AB_WAIT_LGKM0();
+  ATT_WAIT_LGKM0();
 }
 __device__ __forceinline__ bf16x8_t pack8(const f32x16_t& v, int c) {
   return __builtin_bit_cast(bf16x8_t, make_uint4(pack2bf_hw(v[8 * c + 0], v[8 * c + 1]), pack2bf_hw(v[8 * c + 2], v[8 * c + 3]),
@@ -138,7 +134,7 @@ __global__ void __launch_bounds__(256) attn_delta_k(const uint16_t* __restrict__
   int64_t t = 0; int h = 0;
   if (on) {
     t = item / nq; h = (int)(item - t * nq);
-    const int64_t off = t * out_stride + (int64_t)h * AB_D + sub * 8;
+    const int64_t off = t * out_stride + (int64_t)h * ATT_D + sub * 8;
     const uint4 o = *reinterpret_cast<const uint4*>(out + off), g = *reinterpret_cast<const uint4*>(dout + off);
     acc = bflo(o.x) * bflo(g.x) + bfhi(o.x) * bfhi(g.x) + bflo(o.y) * bflo(g.y) + bfhi(o.y) * bfhi(g.y) +
           bflo(o.z) * bflo(g.z) + bfhi(o.z) * bfhi(g.z) + bflo(o.w) * bflo(g.w) + bfhi(o.w) * bfhi(g.w);
@@ -147,10 +143,10 @@ __global__ void __launch_bounds__(256) attn_delta_k(const uint16_t* __restrict__
   for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if (on && sub == 0) {
     if (S == 0) {
-      delta[t * nq + h] = acc;
+      delta[stat_idx(true, t, 0, h, 0, nq, 0)] = acc;        // packed: token t is query 0 of "the sequence that starts at row t"
     } else {
-      const int64_t b = t / S; const int s = (int)(t - b * S);
-      delta[(b * nq + h) * S + s] = acc;
+      const int64_t b = t / S;
+      delta[stat_idx(false, 0, b, h, (int)(t - b * S), nq, S)] = acc;
     }
   }
 }
@@ -174,17 +170,9 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(wave);
-  const int kx = (int)blockIdx.x >> 3;
-  const int set = (kx / nkb) * 8 + ((int)blockIdx.x & 7), kblk = kx % nkb;
-  if (set >= n_sets) return;
-  const int b = set / nkv, hk = set - b * nkv;
+  ATT_WG_DECODE(nkb, kblk)
   const int group = nq / nkv;
-  int S = S_arg;
-  int64_t row0 = (int64_t)b * S_arg;
-  if constexpr (VARLEN) {
-    row0 = cu_seqlens[b];
-    S = cu_seqlens[b + 1] - cu_seqlens[b];
-  }
+  ATT_SEQ_BOUNDS()
   if (kblk * 128 >= S) return;
   const int key = kblk * 128 + wave * 32 + (lane & 31);
   bool key_ok = key < S;
@@ -213,38 +201,24 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
     qt = qt0 + (n - g * per_head);
     h = hk * group + g;
   };
-  // Buffer-addressed LDS-DMA (round 6, as the forward kernel): the descriptor's range check zero-fills rows past the sequence (their
-  // statistics are lse = +inf -> P = 0, so the row's content never matters) -- no per-tile clamp / 64-bit multiply per piece.  The lane's
-  // offset of piece i is [(lane>>4) rows + the swizzled unit of piece 0] ^ (i << 4): the strides are multiples of 256 B, so the unit sits
-  // alone in bits 7:4 and g(row) of piece i differs from piece 0's in bits 5:4 only -- one v_xor per piece from two values that are
-  // recomputed from a laundered lane id in every call (kept across the tile loop they are the first registers hipcc spills, and a
-  // scratch reload's vmcnt wait would sit between the DMA pieces); the piece's 4 i rows, the wave's 16 rows, the tile and the head
-  // go into the scalar offset.
-  const auto q_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(seq_qkv), (short)0, (int)((uint32_t)(S - 1) * qkv_stride_b + (uint32_t)nq * AB_D * 2u), 0x00020000);
-  const auto do_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(seq_do), (short)0, (int)((uint32_t)(S - 1) * out_stride_b + (uint32_t)nq * AB_D * 2u), 0x00020000);
+  // Q and dO tiles through stage_pair: rows past the sequence are zero-filled by the descriptors' range check (their statistics are
+  // lse = +inf -> P = 0, so the row's content never matters)
+  const auto q_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(seq_qkv), (short)0, (int)((uint32_t)(S - 1) * qkv_stride_b + (uint32_t)nq * ATT_D * 2u), 0x00020000);
+  const auto do_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(seq_do), (short)0, (int)((uint32_t)(S - 1) * out_stride_b + (uint32_t)nq * ATT_D * 2u), 0x00020000);
   auto stage = [&](int n, int buf) {
     int h, qt;
     tile_of(n, h, qt);
     char* sb = smem + buf * AB_STAGE + wv * 4096;
-    const uint32_t hq = (uint32_t)__builtin_amdgcn_readfirstlane(h * AB_D * 2), rq = (uint32_t)__builtin_amdgcn_readfirstlane(qt * 64 + 16 * wv);
-    const uint32_t off_q = rq * qkv_stride_b + hq, off_d = rq * out_stride_b + hq;
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    const uint32_t u0_b = (uint32_t)(((ln & 15) ^ (((ln >> 4) & 3) << 2)) << 4);          // g(16w + (lane>>4)) << 4, cf. stage_img
-    const uint32_t xq = (uint32_t)(ln >> 4) * qkv_stride_b + u0_b, xd = (uint32_t)(ln >> 4) * out_stride_b + u0_b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(q_rsrc, (ab_lptr_t)(sb + i * 1024), 16, (int)(xq ^ (uint32_t)(i << 4)), (int)(off_q + 4u * i * qkv_stride_b), 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(do_rsrc, (ab_lptr_t)(sb + AB_IMG + i * 1024), 16, (int)(xd ^ (uint32_t)(i << 4)), (int)(off_d + 4u * i * out_stride_b), 0, 0);
-    }
+    const uint32_t hq = (uint32_t)__builtin_amdgcn_readfirstlane(h * ATT_D * 2), rq = (uint32_t)__builtin_amdgcn_readfirstlane(qt * 64 + 16 * wv);
+    stage_pair(q_rsrc, do_rsrc, qkv_stride_b, out_stride_b, rq * qkv_stride_b + hq, rq * out_stride_b + hq, sb, lane);
   };
   if (ntl > 0) stage(0, 0);
 
   // K, V fragments of the owned key (B operands): X[key][16ks + 8hi .. +8]
   bf16x8_t kf[8], vf[8];
   {
-    const char* kp = seq_qkv + ((uint32_t)key_ld * qkv_stride_b + (uint32_t)((nq + hk) * AB_D * 2 + hi * 16));
-    const char* vp = kp + nkv * AB_D * 2;
+    const char* kp = seq_qkv + ((uint32_t)key_ld * qkv_stride_b + (uint32_t)((nq + hk) * ATT_D * 2 + hi * 16));
+    const char* vp = kp + nkv * ATT_D * 2;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + ks * 32);
@@ -265,7 +239,8 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
     int h_s, qt_s;
     tile_of(n_, h_s, qt_s);
     const int qc = qt_s * 64 + lane < S ? qt_s * 64 + lane : S - 1;
-    // padded layout [B,nq,S] (stride 1 over q), packed layout [T,nq] (stride nq over q)
+    // stat_idx, split into the head's workgroup-uniform part (scalar registers) and the lane's query (stride 1 padded, nq packed); through
+    // stat_idx itself hipcc forms the whole index per lane and the packed instantiations compile to a different stream
     const float* lrow = VARLEN ? lse + row0 * nq + h_s : lse + ((int64_t)b * nq + h_s) * S;
     const float* drow = VARLEN ? delta + row0 * nq + h_s : delta + ((int64_t)b * nq + h_s) * S;
     const int64_t qs = VARLEN ? nq : 1;
@@ -278,7 +253,7 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
   float next_l = 0.f, next_d = 0.f;
   if (ntl > 0) load_stats(0, next_l, next_d);
   for (int n = 0; n < ntl; ++n) {
-    AB_WAIT_VM0();
+    ATT_WAIT_VM0();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     int h_t, qt;
@@ -306,7 +281,7 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
 #pragma unroll
       for (int db = 0; db < 4; ++db) { t0[db] = img_b + (uint32_t)(trl.o0 ^ (db << 6)); t1[db] = img_b + (uint32_t)(trl.o1 ^ (db << 6)); }
       bf16x8_t fa0[3], fa1[3];
-      ab_s16x4_t fbr[2][4][2][2];                                // [group c][db][operand][half]
+      s16x4_t fbr[2][4][2][2];                                // [group c][db][operand][half]
       f32x4_t lq[4], dq4[4];                                     // statistics of the half's rows 8j + 4hi .. +3
       const uint32_t st_base = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)(smem + AB_RING)) + (uint32_t)wv * 512u;
       const uint32_t st_w = st_base + (uint32_t)lane * 4u;
@@ -324,13 +299,12 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
   //  to this form (+1.9 % at S 512, -1.5 % at S 2048: profiles/r03_attn_bwd_ab_asm_reads.log): the moves ride in issue slots the
   //  matrix pipe leaves free.  Not kept.)
 #define DK_MFMA_V0(D, A, B) D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, zero16, 0, 0, 0)
-#define DK_MFMA_V(D, A, B) D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, D, 0, 0, 0)
-#define DK_MFMA_A(D, A, B) D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, D, 0, 0, 0)
+#define DK_MFMA(D, A, B) D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, D, 0, 0, 0)
 #define DK_A_MMA(KS, N)                                                                                                           \
   do {                                                                                                                            \
     asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(fa0[(KS) % 3]), "+v"(fa1[(KS) % 3]) : : "memory");                            \
     if ((KS) == 0) { DK_MFMA_V0(s, fa0[(KS) % 3], kf[KS]); DK_MFMA_V0(dp, fa1[(KS) % 3], vf[KS]); }                               \
-    else { DK_MFMA_V(s, fa0[(KS) % 3], kf[KS]); DK_MFMA_V(dp, fa1[(KS) % 3], vf[KS]); }                                           \
+    else { DK_MFMA(s, fa0[(KS) % 3], kf[KS]); DK_MFMA(dp, fa1[(KS) % 3], vf[KS]); }                                           \
   } while (0)
 #define DK_B_READ1(QB, C, DB, OP)                                                                                                 \
   do {                                                                                                                            \
@@ -358,8 +332,8 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
 #define DK_B_MMA(C)                                                                                                               \
   _Pragma("unroll") for (int db = 0; db < 4; ++db) {                                                                              \
     const bf16x8_t f1_ = DK_FRAG(C, db, 1), f0_ = DK_FRAG(C, db, 0);                                                              \
-    DK_MFMA_A(dv[db], f1_, pb[C]);                                                                                                \
-    DK_MFMA_A(dk[db], f0_, dsb[C]);                                                                                               \
+    DK_MFMA(dv[db], f1_, pb[C]);                                                                                                \
+    DK_MFMA(dk[db], f0_, dsb[C]);                                                                                               \
   }
 // The 64 queries' statistics (lse, delta) reach the lanes that need them -- 16 rows per half and lane, the same for every key column --
 // through a 512-byte per-wave LDS table (round 6): lane l writes the pair of query l once per tile, every lane reads its 4 + 4 aligned
@@ -428,8 +402,7 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
 #undef DK_A_READ
 #undef DK_A_MMA
 #undef DK_MFMA_V0
-#undef DK_MFMA_V
-#undef DK_MFMA_A
+#undef DK_MFMA
 #undef DK_B_READ1
 #undef DK_B_READ
 #undef DK_B_WAIT
@@ -442,13 +415,13 @@ attn_bwd_dkdv_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ k
     }
   }
   // every wave is done with the ring: it becomes the transposition buffer of the full-line gradient stores
-  AB_WAIT_VM0();
+  ATT_WAIT_VM0();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   char* xs = smem + wv * 8192;
   char* seq_dqkv = reinterpret_cast<char*>(dqkv + row0 * qkv_stride);
-  store_tile_rows(dk, scale, xs, seq_dqkv + (int64_t)(nq + hk) * AB_D * 2, qkv_stride_b, kblk * 128 + wave * 32, S, lane);
-  store_tile_rows(dv, 1.0f, xs, seq_dqkv + (int64_t)(nq + nkv + hk) * AB_D * 2, qkv_stride_b, kblk * 128 + wave * 32, S, lane);
+  store_tile_rows(dk, scale, xs, seq_dqkv + (int64_t)(nq + hk) * ATT_D * 2, qkv_stride_b, kblk * 128 + wave * 32, S, lane);
+  store_tile_rows(dv, 1.0f, xs, seq_dqkv + (int64_t)(nq + nkv + hk) * ATT_D * 2, qkv_stride_b, kblk * 128 + wave * 32, S, lane);
 }
 
 // ------------------------------------------------------------------ dQ
@@ -463,27 +436,22 @@ attn_bwd_dq_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ key
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(wave);
-  const int gqa = nq / nkv, U = gqa * nqb;
-  const int kx = (int)blockIdx.x >> 3;
-  const int set = (kx / U) * 8 + ((int)blockIdx.x & 7), member = kx % U;
-  if (set >= n_sets) return;
-  const int b = set / nkv, hk = set - b * nkv;
+  const int gqa = nq / nkv;
+  ATT_WG_DECODE(gqa * nqb, member)
   const int h = hk * gqa + member % gqa, qblk = member / gqa;
-  int S = S_arg;
-  int64_t row0 = (int64_t)b * S_arg;
-  if constexpr (VARLEN) {
-    row0 = cu_seqlens[b];
-    S = cu_seqlens[b + 1] - cu_seqlens[b];
-  }
+  ATT_SEQ_BOUNDS()
   if (qblk * 128 >= S) return;
   const uint32_t qkv_stride_b = (uint32_t)qkv_stride * 2u, out_stride_b = (uint32_t)out_stride * 2u;
   const char* seq_qkv = reinterpret_cast<const char*>(qkv + row0 * qkv_stride);
-  const char* k_base = seq_qkv + (int64_t)(nq + hk) * AB_D * 2;
+  const char* k_base = seq_qkv + (int64_t)(nq + hk) * ATT_D * 2;
   // buffer-addressed LDS-DMA (round 6, cf. attn_bwd_dkdv_k): ONE descriptor serves K and V (same row stride; V sits v_delta bytes behind
   // K, a scalar), rows past the sequence are zero-filled by the range check (their keys are masked by the tile's key word)
-  const uint32_t v_delta_b = (uint32_t)nkv * AB_D * 2u;
+  const uint32_t v_delta_b = (uint32_t)nkv * ATT_D * 2u;
   const auto kv_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(k_base), (short)0, (int)((uint32_t)(S - 1) * qkv_stride_b + 256u + v_delta_b), 0x00020000);
   auto stage = [&](int t, int buf) {
+    // stage_pair with one descriptor and one stride, written out: through stage_pair itself hipcc orders the address arithmetic
+    // differently (75 / 73 lines of the instruction stream), and an A/B of that build put two of eight legs 0.1-0.2 % above the parent's
+    // range (profiles/attn_bwd_refactor_ab.json) -- this kernel sits at exactly 256 registers, so its stream stays the measured one
     char* sb = smem + buf * AB_STAGE + wv * 4096;
     const uint32_t off_k = (uint32_t)__builtin_amdgcn_readfirstlane(t * 64 + 16 * wv) * qkv_stride_b;
     int ln = lane;
@@ -492,8 +460,8 @@ attn_bwd_dq_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ key
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const uint32_t vo = xk ^ (uint32_t)(i << 4), so = off_k + 4u * i * qkv_stride_b;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(kv_rsrc, (ab_lptr_t)(sb + i * 1024), 16, (int)vo, (int)so, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(kv_rsrc, (ab_lptr_t)(sb + AB_IMG + i * 1024), 16, (int)vo, (int)(so + v_delta_b), 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(kv_rsrc, (att_lptr_t)(sb + i * 1024), 16, (int)vo, (int)so, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(kv_rsrc, (att_lptr_t)(sb + AB_IMG + i * 1024), 16, (int)vo, (int)(so + v_delta_b), 0, 0);
     }
   };
   // first K/V tile: 0 (always exists: S > 0), or the one holding the first key of the block's first query's window
@@ -514,14 +482,14 @@ attn_bwd_dq_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ key
   const int q = qblk * 128 + wave * 32 + (lane & 31);
   const int q_ld = q < S ? q : S - 1;
   const float scale_log2 = scale * 1.4426950408889634f;
-  const int64_t sidx = VARLEN ? (row0 + q_ld) * nq + h : ((int64_t)b * nq + h) * S + q_ld;
+  const int64_t sidx = stat_idx(VARLEN, row0, b, h, q_ld, nq, S);
   const float lse2 = lse[sidx] * 1.4426950408889634f;
   const float dlt = delta[sidx];
 
   bf16x8_t qf[8], dof[8];
   {
-    const char* qp = seq_qkv + ((uint32_t)q_ld * qkv_stride_b + (uint32_t)(h * AB_D * 2 + hi * 16));
-    const char* dp = reinterpret_cast<const char*>(dout + row0 * out_stride) + ((uint32_t)q_ld * out_stride_b + (uint32_t)(h * AB_D * 2 + hi * 16));
+    const char* qp = seq_qkv + ((uint32_t)q_ld * qkv_stride_b + (uint32_t)(h * ATT_D * 2 + hi * 16));
+    const char* dp = reinterpret_cast<const char*>(dout + row0 * out_stride) + ((uint32_t)q_ld * out_stride_b + (uint32_t)(h * ATT_D * 2 + hi * 16));
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + ks * 32);
@@ -542,7 +510,7 @@ attn_bwd_dq_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ key
     if (t_first < ntiles) word_next = bits[t_first];
   }
   for (int t = t_first; t < ntiles; ++t) {
-    AB_WAIT_VM0();
+    ATT_WAIT_VM0();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     const char* k_img = smem + (t & 1) * AB_STAGE;
@@ -643,10 +611,10 @@ attn_bwd_dq_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ key
     //  must not sit inside the pinned read groups; here its round trip overlaps the wait for the next tile's DMA and the barrier)
     if constexpr (!VARLEN) word_next = bits[t + 1 < ntiles ? t + 1 : t];
   }
-  AB_WAIT_VM0();
+  ATT_WAIT_VM0();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  store_tile_rows(dq, scale, smem + wv * 8192, reinterpret_cast<char*>(dqkv + row0 * qkv_stride) + (int64_t)h * AB_D * 2, qkv_stride_b,
+  store_tile_rows(dq, scale, smem + wv * 8192, reinterpret_cast<char*>(dqkv + row0 * qkv_stride) + (int64_t)h * ATT_D * 2, qkv_stride_b,
                   qblk * 128 + wave * 32, S, lane);
 }
 
@@ -654,120 +622,99 @@ attn_bwd_dq_k(const uint16_t* __restrict__ qkv, const uint64_t* __restrict__ key
 
 using namespace grit;
 
-static int attn_bwd_launch(bool varlen, int causal, int window, const void* qkv, const uint64_t* key_bits, const int32_t* cu, const void* out, const void* dout,
-                           const float* lse, float* delta, void* dqkv, int B, int S_or_maxlen, int64_t T, int nq, int nkv,
-                           int64_t qkv_stride, int64_t out_stride, float scale, hipStream_t st) {
+// The three launches: delta, dK/dV ([varlen][cw]: the CW = false instantiations serve bidirectional attention), dQ ([varlen]); every
+// instantiation of the two MFMA kernels takes the same arguments (nblk: the 128-row blocks of the longest sequence, keys or queries).
+typedef void (*attn_bwd_kernel_t)(const uint16_t*, const uint64_t*, const int32_t*, const uint16_t*, const float*, const float*, uint16_t*, int, int,
+                                  int, int64_t, int64_t, float, int, int, int, int);
+#define AB_CHECK_LAUNCH(what)                                                                           \
+  do {                                                                                                  \
+    const hipError_t e__ = hipGetLastError();                                                           \
+    if (e__ != hipSuccess) {                                                                            \
+      ::grit::set_error("%s: " what ": launch failed: %s", name, hipGetErrorString(e__));               \
+      return GRIT_E_LAUNCH;                                                                             \
+    }                                                                                                   \
+  } while (0)
+static int attn_bwd_launch(const char* name, bool varlen, int causal, int window, const uint16_t* qkv, const uint64_t* key_bits, const int32_t* cu,
+                           const uint16_t* out, const uint16_t* dout, const float* lse, float* delta, uint16_t* dqkv, int B, int S_or_maxlen, int64_t T,
+                           int nq, int nkv, int64_t qkv_stride, int64_t out_stride, float scale, hipStream_t st) {
+  static const attn_bwd_kernel_t dkdv[2][2] = {{attn_bwd_dkdv_k<false, false>, attn_bwd_dkdv_k<false, true>},
+                                               {attn_bwd_dkdv_k<true, false>, attn_bwd_dkdv_k<true, true>}};
+  static const attn_bwd_kernel_t dq[2] = {attn_bwd_dq_k<false>, attn_bwd_dq_k<true>};
+  static std::atomic<uint64_t> optin[2][2];
   const int64_t items = T * nq;
-  hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)((items * 16 + 255) / 256)), dim3(256), 0, st, (const uint16_t*)out,
-                     (const uint16_t*)dout, delta, T, varlen ? 0 : S_or_maxlen, nq, out_stride);
-  GRIT_CHECK_LAUNCH("grit_attn_bidir_bwd: delta");
+  hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)((items * 16 + 255) / 256)), dim3(256), 0, st, out, dout, delta, T, varlen ? 0 : S_or_maxlen, nq,
+                     out_stride);
+  AB_CHECK_LAUNCH("delta");
   const int lds_kv = AB_RING + 4 * 512;          // ring + the four waves' statistics tables (attn_bwd_dkdv_k)
-  static std::atomic<uint64_t> optin{0};                       // per-device function attribute
-  {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(optin.load(std::memory_order_acquire) & bit)) {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_k<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_k<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_k<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_k<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv);
-      optin.fetch_or(bit, std::memory_order_release);
-    }
-  }
+  const bool cw = causal != 0 || window > 0;
+  attn_lds_optin(dkdv[varlen][cw], optin[varlen][cw], lds_kv);
   const int nblk = (S_or_maxlen + 127) / 128;
   const int n_sets = B * nkv, sets8 = 8 * ((n_sets + 7) / 8);
-  const dim3 grid_kv((unsigned)(sets8 * nblk)), grid_q((unsigned)(sets8 * (nq / nkv) * nblk));
-#define AB_LAUNCH_KV(VL, CWF)                                                                                                       \
-  hipLaunchKernelGGL((attn_bwd_dkdv_k<VL, CWF>), grid_kv, dim3(256), lds_kv, st, (const uint16_t*)qkv, key_bits, cu, (const uint16_t*)dout, lse,  \
-                     delta, (uint16_t*)dqkv, S_or_maxlen, nq, nkv, qkv_stride, out_stride, scale, causal, nblk, n_sets, window)
-  const bool cw = causal != 0 || window > 0;
-  if (varlen) {
-    if (cw) { AB_LAUNCH_KV(true, true); } else { AB_LAUNCH_KV(true, false); }
-    GRIT_CHECK_LAUNCH("grit_attn_bidir_varlen_bwd: dkdv");
-    hipLaunchKernelGGL(attn_bwd_dq_k<true>, grid_q, dim3(256), 0, st, (const uint16_t*)qkv, key_bits, cu,
-                       (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, S_or_maxlen, nq, nkv, qkv_stride, out_stride, scale, causal, nblk, n_sets, window);
-    GRIT_CHECK_LAUNCH("grit_attn_bidir_varlen_bwd: dq");
-  } else {
-    if (cw) { AB_LAUNCH_KV(false, true); } else { AB_LAUNCH_KV(false, false); }
-    GRIT_CHECK_LAUNCH("grit_attn_bidir_bwd: dkdv");
-    hipLaunchKernelGGL(attn_bwd_dq_k<false>, grid_q, dim3(256), 0, st, (const uint16_t*)qkv, key_bits, cu,
-                       (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, S_or_maxlen, nq, nkv, qkv_stride, out_stride, scale, causal, nblk, n_sets, window);
-    GRIT_CHECK_LAUNCH("grit_attn_bidir_bwd: dq");
-  }
-#undef AB_LAUNCH_KV
+  hipLaunchKernelGGL(dkdv[varlen][cw], dim3((unsigned)(sets8 * nblk)), dim3(256), lds_kv, st, qkv, key_bits, cu, dout, lse, delta, dqkv, S_or_maxlen, nq,
+                     nkv, qkv_stride, out_stride, scale, causal, nblk, n_sets, window);
+  AB_CHECK_LAUNCH("dkdv");
+  hipLaunchKernelGGL(dq[varlen], dim3((unsigned)(sets8 * (nq / nkv) * nblk)), dim3(256), 0, st, qkv, key_bits, cu, dout, lse, delta, dqkv, S_or_maxlen,
+                     nq, nkv, qkv_stride, out_stride, scale, causal, nblk, n_sets, window);
+  AB_CHECK_LAUNCH("dq");
   return GRIT_OK;
 }
+#undef AB_CHECK_LAUNCH
 
-static int attn_bwd_padded(int causal, int window, const void* qkv, const uint64_t* key_bits, const void* out, const void* dout, const float* lse,
-                           float* delta, void* dqkv, int B, int S, int nq, int nkv, int d, int64_t qkv_stride,
-                           int64_t out_stride, float scale, void* stream) {
-  GRIT_REQUIRE(qkv && key_bits && out && dout && lse && delta && dqkv, GRIT_E_BADARG, "grit_attn_bidir_bwd: null pointer");
-  GRIT_REQUIRE(B > 0 && S > 0 && nq > 0 && nkv > 0 && S <= (1 << 30) && nq <= 65535 && nkv <= 65535, GRIT_E_BADARG, "grit_attn_bidir_bwd: bad sizes");
-  GRIT_REQUIRE(d == AB_D, GRIT_E_UNSUPPORTED, "grit_attn_bidir_bwd: head_dim=%d (only 128 is built)", d);
-  GRIT_REQUIRE(nq % nkv == 0, GRIT_E_BADARG, "grit_attn_bidir_bwd: nq not a multiple of nkv");
-  GRIT_REQUIRE(window >= 0 && (causal || window == 0), GRIT_E_BADARG, "grit_attn_bidir_bwd: window=%d (causal attention only)", window);
+// Padded batches (varlen = false: S rows per sequence, key_bits, T = B S) and packed ones (varlen = true: cu_seqlens, S = the longest sequence).
+static int attn_bwd(const char* name, bool varlen, int causal, int window, const void* qkv, const uint64_t* key_bits, const int32_t* cu_seqlens,
+                    const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int S, int64_t T, int nq, int nkv, int d,
+                    int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
+  GRIT_REQUIRE(qkv && (varlen ? (const void*)cu_seqlens : key_bits) && out && dout && lse && delta && dqkv, GRIT_E_BADARG, "%s: null pointer", name);
+  GRIT_REQUIRE(B > 0 && S > 0 && T > 0 && nq > 0 && nkv > 0 && S <= (1 << 30) && nq <= 65535 && nkv <= 65535, GRIT_E_BADARG, "%s: bad sizes", name);
+  GRIT_REQUIRE(d == ATT_D, GRIT_E_UNSUPPORTED, "%s: head_dim=%d (only 128 is built)", name, d);
+  GRIT_REQUIRE(nq % nkv == 0, GRIT_E_BADARG, "%s: nq not a multiple of nkv", name);
+  GRIT_REQUIRE(window >= 0 && (causal || window == 0), GRIT_E_BADARG, "%s: window=%d (causal attention only)", name, window);
   GRIT_REQUIRE(qkv_stride % 8 == 0 && qkv_stride >= (int64_t)(nq + 2 * nkv) * d && out_stride % 8 == 0 && out_stride >= (int64_t)nq * d,
-               GRIT_E_BADARG, "grit_attn_bidir_bwd: bad strides");
-  GRIT_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv), GRIT_E_BADARG,
-               "grit_attn_bidir_bwd: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)B * nq * ((S + 127) / 128) < (1ll << 30), GRIT_E_UNSUPPORTED, "grit_attn_bidir_bwd: grid too large");
+               GRIT_E_BADARG, "%s: bad strides", name);
+  GRIT_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", name);
+  GRIT_REQUIRE((int64_t)B * nq * ((S + 127) / 128) < (1ll << 30), GRIT_E_UNSUPPORTED, "%s: grid too large", name);
   GRIT_REQUIRE((int64_t)S * qkv_stride * 2 < (1ll << 31) && (int64_t)S * out_stride * 2 < (1ll << 31), GRIT_E_UNSUPPORTED,
-               "grit_attn_bidir_bwd: one sequence spans more than 2 GiB (32-bit row offsets)");
-  return attn_bwd_launch(false, causal, window, qkv, key_bits, nullptr, out, dout, lse, delta, dqkv, B, S, (int64_t)B * S, nq, nkv, qkv_stride,
-                         out_stride, scale, (hipStream_t)stream);
+               "%s: one sequence spans more than 2 GiB (32-bit row offsets)", name);
+  return attn_bwd_launch(name, varlen, causal, window, (const uint16_t*)qkv, key_bits, cu_seqlens, (const uint16_t*)out, (const uint16_t*)dout, lse,
+                         delta, (uint16_t*)dqkv, B, S, T, nq, nkv, qkv_stride, out_stride, scale, (hipStream_t)stream);
 }
+
 extern "C" int grit_attn_bidir_bwd(const void* qkv, const uint64_t* key_bits, const void* out, const void* dout, const float* lse,
                                    float* delta, void* dqkv, int B, int S, int nq, int nkv, int d, int64_t qkv_stride,
                                    int64_t out_stride, float scale, void* stream) {
-  return attn_bwd_padded(0, 0, qkv, key_bits, out, dout, lse, delta, dqkv, B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
+  return attn_bwd("grit_attn_bidir_bwd", false, 0, 0, qkv, key_bits, nullptr, out, dout, lse, delta, dqkv, B, S, (int64_t)B * S, nq, nkv, d, qkv_stride,
+                  out_stride, scale, stream);
 }
 extern "C" int grit_attn_causal_bwd(const void* qkv, const uint64_t* key_bits, const void* out, const void* dout, const float* lse,
                                     float* delta, void* dqkv, int B, int S, int nq, int nkv, int d, int64_t qkv_stride,
                                     int64_t out_stride, float scale, void* stream) {
-  return attn_bwd_padded(1, 0, qkv, key_bits, out, dout, lse, delta, dqkv, B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
-}
-
-static int attn_bwd_varlen(int causal, int window, const void* qkv, const int32_t* cu_seqlens, const void* out, const void* dout, const float* lse,
-                           float* delta, void* dqkv, int B, int max_len, int64_t T, int nq, int nkv, int d,
-                           int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  GRIT_REQUIRE(qkv && cu_seqlens && out && dout && lse && delta && dqkv, GRIT_E_BADARG, "grit_attn_bidir_varlen_bwd: null pointer");
-  GRIT_REQUIRE(B > 0 && max_len > 0 && T > 0 && nq > 0 && nkv > 0 && max_len <= (1 << 30) && nq <= 65535 && nkv <= 65535, GRIT_E_BADARG,
-               "grit_attn_bidir_varlen_bwd: bad sizes");
-  GRIT_REQUIRE(d == AB_D, GRIT_E_UNSUPPORTED, "grit_attn_bidir_varlen_bwd: head_dim=%d (only 128 is built)", d);
-  GRIT_REQUIRE(nq % nkv == 0, GRIT_E_BADARG, "grit_attn_bidir_varlen_bwd: nq not a multiple of nkv");
-  GRIT_REQUIRE(window >= 0 && (causal || window == 0), GRIT_E_BADARG, "grit_attn_bidir_varlen_bwd: window=%d (causal attention only)", window);
-  GRIT_REQUIRE(qkv_stride % 8 == 0 && qkv_stride >= (int64_t)(nq + 2 * nkv) * d && out_stride % 8 == 0 && out_stride >= (int64_t)nq * d,
-               GRIT_E_BADARG, "grit_attn_bidir_varlen_bwd: bad strides");
-  GRIT_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv), GRIT_E_BADARG,
-               "grit_attn_bidir_varlen_bwd: pointers must be 16-byte aligned");
-  GRIT_REQUIRE((int64_t)B * nq * ((max_len + 127) / 128) < (1ll << 30), GRIT_E_UNSUPPORTED, "grit_attn_bidir_varlen_bwd: grid too large");
-  GRIT_REQUIRE((int64_t)max_len * qkv_stride * 2 < (1ll << 31) && (int64_t)max_len * out_stride * 2 < (1ll << 31), GRIT_E_UNSUPPORTED,
-               "grit_attn_bidir_varlen_bwd: one sequence spans more than 2 GiB (32-bit row offsets)");
-  return attn_bwd_launch(true, causal, window, qkv, nullptr, cu_seqlens, out, dout, lse, delta, dqkv, B, max_len, T, nq, nkv, qkv_stride, out_stride,
-                         scale, (hipStream_t)stream);
+  return attn_bwd("grit_attn_causal_bwd", false, 1, 0, qkv, key_bits, nullptr, out, dout, lse, delta, dqkv, B, S, (int64_t)B * S, nq, nkv, d, qkv_stride,
+                  out_stride, scale, stream);
 }
 extern "C" int grit_attn_bidir_varlen_bwd(const void* qkv, const int32_t* cu_seqlens, const void* out, const void* dout, const float* lse,
                                           float* delta, void* dqkv, int B, int max_len, int64_t T, int nq, int nkv, int d,
                                           int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_bwd_varlen(0, 0, qkv, cu_seqlens, out, dout, lse, delta, dqkv, B, max_len, T, nq, nkv, d, qkv_stride, out_stride, scale, stream);
+  return attn_bwd("grit_attn_bidir_varlen_bwd", true, 0, 0, qkv, nullptr, cu_seqlens, out, dout, lse, delta, dqkv, B, max_len, T, nq, nkv, d, qkv_stride,
+                  out_stride, scale, stream);
 }
 extern "C" int grit_attn_causal_varlen_bwd(const void* qkv, const int32_t* cu_seqlens, const void* out, const void* dout, const float* lse,
                                            float* delta, void* dqkv, int B, int max_len, int64_t T, int nq, int nkv, int d,
                                            int64_t qkv_stride, int64_t out_stride, float scale, void* stream) {
-  return attn_bwd_varlen(1, 0, qkv, cu_seqlens, out, dout, lse, delta, dqkv, B, max_len, T, nq, nkv, d, qkv_stride, out_stride, scale, stream);
+  return attn_bwd("grit_attn_causal_varlen_bwd", true, 1, 0, qkv, nullptr, cu_seqlens, out, dout, lse, delta, dqkv, B, max_len, T, nq, nkv, d, qkv_stride,
+                  out_stride, scale, stream);
 }
 // backward of grit_attn_causal_window_fwd / _varlen_fwd (same window: keys q - window + 1 .. q)
 extern "C" int grit_attn_causal_window_bwd(const void* qkv, const uint64_t* key_bits, const void* out, const void* dout, const float* lse,
                                            float* delta, void* dqkv, int B, int S, int nq, int nkv, int d, int64_t qkv_stride,
                                            int64_t out_stride, float scale, int window, void* stream) {
   GRIT_REQUIRE(window >= 1, GRIT_E_BADARG, "grit_attn_causal_window_bwd: window=%d must be >= 1", window);
-  return attn_bwd_padded(1, window, qkv, key_bits, out, dout, lse, delta, dqkv, B, S, nq, nkv, d, qkv_stride, out_stride, scale, stream);
+  return attn_bwd("grit_attn_causal_window_bwd", false, 1, window, qkv, key_bits, nullptr, out, dout, lse, delta, dqkv, B, S, (int64_t)B * S, nq, nkv, d,
+                  qkv_stride, out_stride, scale, stream);
 }
 extern "C" int grit_attn_causal_window_varlen_bwd(const void* qkv, const int32_t* cu_seqlens, const void* out, const void* dout,
                                                   const float* lse, float* delta, void* dqkv, int B, int max_len, int64_t T, int nq, int nkv,
                                                   int d, int64_t qkv_stride, int64_t out_stride, float scale, int window, void* stream) {
   GRIT_REQUIRE(window >= 1, GRIT_E_BADARG, "grit_attn_causal_window_varlen_bwd: window=%d must be >= 1", window);
-  return attn_bwd_varlen(1, window, qkv, cu_seqlens, out, dout, lse, delta, dqkv, B, max_len, T, nq, nkv, d, qkv_stride, out_stride, scale,
-                         stream);
+  return attn_bwd("grit_attn_causal_window_varlen_bwd", true, 1, window, qkv, nullptr, cu_seqlens, out, dout, lse, delta, dqkv, B, max_len, T, nq, nkv,
+                  d, qkv_stride, out_stride, scale, stream);
 }

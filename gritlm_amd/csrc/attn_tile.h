@@ -1,6 +1,8 @@
 // The MFMA tile loop of the flash-attention forward kernels for gfx950 (head_dim 128): the LDS layout, the per-tile consumer and the
 // output epilogue, shared by attn_bidir_fwd_k (attention.hip) and attn_prefill_cached_k (prefill.hip).  Each kernel keeps its own
 // tile ranges, mask words, K/V staging and Q loads.  The tile consumer and the epilogue are statement macros (below: why).
+// The backward (attention_bwd.hip) has its own tile loops and takes from here what every attention kernel shares: the wait macros, the
+// address-space types, the workgroup prologue (ATT_WG_DECODE, ATT_SEQ_BOUNDS) and the LDS opt-in.
 //
 // A wave owns 32 query rows.  KV tiles of 64 keys are staged HBM -> LDS by the kernel (LDS-DMA, 16 B per lane, 1 KiB = 4 key rows per
 // wave instruction) into a two-stage ring; the eight pieces of tile t+1 are issued BETWEEN the QK products of tile t and land under its
@@ -62,6 +64,29 @@ typedef const __attribute__((address_space(1))) void* att_gptr_t;
 typedef __attribute__((address_space(3))) void* att_lptr_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+
+// ---- The prologue every attention kernel (forward, cached prefill, backward) starts with.
+// XCD-aware decode of the 1-D grid (block v runs on XCD v % 8): the k-th workgroup of XCD x belongs to K/V set (k / U) * 8 + x, U = the
+// workgroups that share one set's streamed operands.  Declares `member` (the workgroup's index inside its set), b and hk (the set's
+// batch and kv head) from n_sets and nkv in scope, and RETURNS from the kernel for the grid's padding (sets are rounded up to 8).
+// A statement macro like the tile consumer below, for the same reason: as a __forceinline__ function (every form tried: the exit test
+// in the caller, in the callee, the results as references or as a struct) hipcc leaves set / nkv in front of the exit branch or tests
+// the exit twice, and the kernels whose first use of nkv lies behind that branch (attn_bwd_dkdv_k) compile to a different stream.
+#define ATT_WG_DECODE(U, member)                                                                                                             \
+  const int att_u = (U), att_kx = (int)blockIdx.x >> 3;                                                                                      \
+  const int att_set = (att_kx / att_u) * 8 + ((int)blockIdx.x & 7), member = att_kx % att_u;                                                 \
+  if (att_set >= n_sets) return;                                                                                                             \
+  const int b = att_set / nkv, hk = att_set - b * nkv;
+// Declares the first row (row0) and the length (S) of sequence b, from b, S_arg, cu_seqlens and VARLEN in scope: padded batches hold
+// S_arg rows per sequence, packed ones (VARLEN) the rows cu_seqlens[b] .. cu_seqlens[b + 1] - 1.  (A macro too: as a function the padded
+// forward instantiations allocate their registers differently.)
+#define ATT_SEQ_BOUNDS()                                                                                                                     \
+  int S = S_arg;                                                                                                                             \
+  int64_t row0 = (int64_t)b * S_arg;                                                                                                         \
+  if constexpr (VARLEN) {                                                                                                                    \
+    row0 = cu_seqlens[b];                                                                                                                    \
+    S = cu_seqlens[b + 1] - cu_seqlens[b];                                                                                                   \
+  }
 
 __device__ __forceinline__ f32x16_t mma32(bf16x8_t a, bf16x8_t b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16_t mma32(f16x8_t a, f16x8_t b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
@@ -303,14 +328,15 @@ template <> struct att_frag<true> { typedef f16x8_t type; };
 
 }  // namespace grit
 
-// the 80 KiB dynamic-LDS opt-in is a per-device function attribute: set it once per (instantiation, device)
+// the dynamic-LDS opt-in (the forward's 80 KiB unless `bytes` says otherwise) is a per-device function attribute: set it once per
+// (instantiation, device)
 template <typename KernelT>
-static void attn_lds_optin(KernelT kernel, std::atomic<uint64_t>& done) {
+static void attn_lds_optin(KernelT kernel, std::atomic<uint64_t>& done, int bytes = grit::ATT_LDS_BYTES) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   const uint64_t bit = 1ull << (dev & 63);
   if (!(done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, grit::ATT_LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     done.fetch_or(bit, std::memory_order_release);
   }
 }

@@ -29,12 +29,8 @@ attn_prefill_cached_k(const uint16_t* __restrict__ q, const uint16_t* __restrict
   typedef typename att_frag<F16>::type frag_t;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware decode: the k-th workgroup of XCD x belongs to K/V set (k / U) * 8 + x, U = (heads per kv head) x (query blocks)
-  const int gqa = nq / nkv, U = gqa * nqb;
-  const int kx = (int)blockIdx.x >> 3;
-  const int set = (kx / U) * 8 + ((int)blockIdx.x & 7), member = kx % U;
-  if (set >= n_sets) return;
-  const int b = set / nkv, hk = set - b * nkv;
+  const int gqa = nq / nkv;
+  ATT_WG_DECODE(gqa * nqb, member)                // U = (heads per kv head) x (query blocks)
   const int h = hk * gqa + member % gqa;
   const int qb = member / gqa;
   int pl = plen[b], L0 = lens[b];

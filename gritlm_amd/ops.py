@@ -158,14 +158,38 @@ def rope_qk_pos_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, positi
     return qkv
 
 
-def _attn_entry(kind: str, causal: bool, window: int):
-    """(entry point, extra arguments) of an attention call: bidirectional, causal, or causal with a sliding window of ``window`` keys."""
-    lib = _lib.load()
-    if window and window > 0:
-        if not causal:
-            raise ValueError("a sliding window applies to causal attention only (the bidirectional embedding path ignores it, as the reference)")
-        return getattr(lib, "grit_attn_causal_window_" + kind), (int(window),)
-    return getattr(lib, ("grit_attn_causal_" if causal else "grit_attn_bidir_") + kind), ()
+def _attn_entry(kind: str, causal: bool, window: int, f16: bool = False):
+    """(entry point's name, extra arguments) of an attention call: bidirectional, causal, or causal with a sliding window of ``window`` keys.
+    ``f16`` (forward only): the fp16-operand entry points, whose causal form takes the window (0: none) as an argument."""
+    window = int(window or 0)
+    if window > 0 and not causal:
+        raise ValueError("a sliding window applies to causal attention only (the bidirectional embedding path ignores it, as the reference)")
+    if f16:
+        return ("grit_attn_causal_" if causal else "grit_attn_bidir_") + kind.replace("fwd", "f16_fwd"), ((window,) if causal else ())
+    if window > 0:
+        return "grit_attn_causal_window_" + kind, (window,)
+    return ("grit_attn_causal_" if causal else "grit_attn_bidir_") + kind, ()
+
+
+def _attn_fwd(kind: str, qkv, layout, layout_name: str, sizes: tuple, flops, nq: int, nkv: int, d: int, out, scale, lse, causal: bool, window: int):
+    """What the padded and the packed forward share: ``layout`` is key_bits or cu_seqlens, ``sizes`` the (B, S) or (B, max_len) in front of
+    nq; ``flops`` (a number, or a callable for a count that costs device work) feeds the timer span."""
+    T, stride = qkv.shape
+    if out is None:
+        out = torch.empty((T, nq * d), dtype=qkv.dtype, device=qkv.device)
+    if scale is None:
+        scale = d ** -0.5
+    ev = _timer.span("attn_bidir_fwd", flops() if callable(flops) else flops) if _timer is not None else None
+    if ev:
+        ev[0].record()
+    odt = F16 if qkv.dtype == F16 else BF16            # fp16: the fp16-operand policies
+    name, wa = _attn_entry(kind, causal, window, odt == F16)
+    check(getattr(_lib.load(), name)(_chk(qkv, odt, "qkv"), _chk(layout, I32 if kind.startswith("varlen") else I64, layout_name), _chk(out, odt, "out"),
+                                     0 if lse is None else _chk(lse, F32, "lse"), *sizes, nq, nkv, d, stride, out.stride(0), float(scale), *wa,
+                                     _stream()), name)
+    if ev:
+        ev[1].record()
+    return out
 
 
 def attn_bidir_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, nq: int, nkv: int, d: int,
@@ -173,30 +197,11 @@ def attn_bidir_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int,
                       causal: bool = False, window: int = 0) -> torch.Tensor:
     """lse (optional, fp32 [T, nq]) receives the log-sum-exp rows for grit_attn_bidir_varlen_bwd.  ``window`` > 0 (causal only): sliding
     window, a query sees keys q - window + 1 .. q."""
-    T, stride = qkv.shape
-    B = cu_seqlens.numel() - 1
-    if out is None:
-        out = torch.empty((T, nq * d), dtype=qkv.dtype, device=qkv.device)
-    if scale is None:
-        scale = d ** -0.5
-    ev = None
-    if _timer is not None:           # algorithmic FLOPs of the packed launch: 4 d nq sum(len^2) (half of it when causal), summed on the device
+    def flops():         # algorithmic FLOPs of the packed launch: 4 d nq sum(len^2) (half of it when causal), summed on the device
         lens = (cu_seqlens[1:] - cu_seqlens[:-1]).double()
-        ev = _timer.span("attn_bidir_fwd", (lens * lens).sum() * (4.0 * nq * d * (0.5 if causal else 1.0)))
-    if ev:
-        ev[0].record()
-    fn, wa = _attn_entry("varlen_fwd", causal, window)
-    odt = BF16
-    if qkv.dtype == F16:            # the fp16-operand policies
-        if window and window > 0 and not causal:
-            raise ValueError("a sliding window applies to causal attention only")
-        fn, wa, odt = (_lib.load().grit_attn_causal_varlen_f16_fwd, (int(window or 0),), F16) if causal else (_lib.load().grit_attn_bidir_varlen_f16_fwd, (), F16)
-    check(fn(_chk(qkv, odt, "qkv"), _chk(cu_seqlens, I32, "cu_seqlens"), _chk(out, odt, "out"),
-             0 if lse is None else _chk(lse, F32, "lse"), B, int(max_len), nq, nkv, d, stride, out.stride(0), float(scale), *wa, _stream()),
-          "grit_attn_bidir_varlen_fwd")
-    if ev:
-        ev[1].record()
-    return out
+        return (lens * lens).sum() * (4.0 * nq * d * (0.5 if causal else 1.0))
+    return _attn_fwd("varlen_fwd", qkv, cu_seqlens, "cu_seqlens", (cu_seqlens.numel() - 1, int(max_len)), flops, nq, nkv, d, out, scale, lse, causal,
+                     window)
 
 
 def pool_norm_varlen(hidden: torch.Tensor, cu_seqlens: torch.Tensor, method: str, normalize: bool,
@@ -463,26 +468,8 @@ def mask_pack(mask: torch.Tensor) -> torch.Tensor:
 def attn_bidir(qkv: torch.Tensor, key_bits: torch.Tensor, B: int, S: int, nq: int, nkv: int, d: int,
                out: torch.Tensor | None = None, lse: torch.Tensor | None = None, scale: float | None = None,
                causal: bool = False, window: int = 0) -> torch.Tensor:
-    T, stride = qkv.shape
-    assert T == B * S
-    if out is None:
-        out = torch.empty((T, nq * d), dtype=qkv.dtype, device=qkv.device)
-    if scale is None:
-        scale = d ** -0.5
-    ev = _timer.span("attn_bidir_fwd", 4.0 * B * nq * S * S * d) if _timer is not None else None
-    if ev:
-        ev[0].record()
-    fn, wa = _attn_entry("fwd", causal, window)
-    odt = BF16
-    if qkv.dtype == F16:            # the fp16-operand policies
-        if window and window > 0 and not causal:
-            raise ValueError("a sliding window applies to causal attention only")
-        fn, wa, odt = (_lib.load().grit_attn_causal_f16_fwd, (int(window or 0),), F16) if causal else (_lib.load().grit_attn_bidir_f16_fwd, (), F16)
-    check(fn(_chk(qkv, odt, "qkv"), _chk(key_bits, I64, "key_bits"), _chk(out, odt, "out"),
-             0 if lse is None else _chk(lse, F32, "lse"), B, S, nq, nkv, d, stride, out.stride(0), float(scale), *wa, _stream()), "grit_attn_bidir_fwd")
-    if ev:
-        ev[1].record()
-    return out
+    assert qkv.shape[0] == B * S
+    return _attn_fwd("fwd", qkv, key_bits, "key_bits", (B, S), 4.0 * B * nq * S * S * d, nq, nkv, d, out, scale, lse, causal, window)
 
 
 def pool_norm(hidden: torch.Tensor, mask: torch.Tensor, method: str, normalize: bool, instr_len: torch.Tensor | None = None,
@@ -576,37 +563,34 @@ def swiglu_bwd(gu: torch.Tensor, dact: torch.Tensor, out: torch.Tensor | None = 
     return out
 
 
-def attn_bidir_bwd(qkv: torch.Tensor, key_bits: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, B: int, S: int,
-                   nq: int, nkv: int, d: int, dqkv: torch.Tensor | None = None, scale: float | None = None,
-                   causal: bool = False, window: int = 0) -> torch.Tensor:
-    T, stride = qkv.shape
+def _attn_bwd(kind: str, qkv, layout, layout_name: str, sizes: tuple, delta_shape: tuple, out, dout, lse, nq: int, nkv: int, d: int, dqkv, scale,
+              causal: bool, window: int):
+    """What the padded and the packed backward share: ``sizes`` is (B, S) or (B, max_len, T); delta is the kernels' scratch."""
+    stride = qkv.shape[1]
     if dqkv is None:
         dqkv = torch.empty_like(qkv)
     if scale is None:
         scale = d ** -0.5
-    delta = torch.empty((B, nq, S), dtype=F32, device=qkv.device)
-    fn, wa = _attn_entry("bwd", causal, window)
-    check(fn(_chk(qkv, BF16, "qkv"), _chk(key_bits, I64, "key_bits"), _chk(out, BF16, "out"), _chk(dout, BF16, "dout"), _chk(lse, F32, "lse"),
-             delta.data_ptr(), _chk(dqkv, BF16, "dqkv"), B, S, nq, nkv, d, stride, out.stride(0), float(scale), *wa, _stream()),
-          "grit_attn_bidir_bwd")
+    delta = torch.empty(delta_shape, dtype=F32, device=qkv.device)
+    name, wa = _attn_entry(kind, causal, window)
+    check(getattr(_lib.load(), name)(_chk(qkv, BF16, "qkv"), _chk(layout, I32 if kind.startswith("varlen") else I64, layout_name), _chk(out, BF16, "out"),
+                                     _chk(dout, BF16, "dout"), _chk(lse, F32, "lse"), delta.data_ptr(), _chk(dqkv, BF16, "dqkv"), *sizes, nq, nkv, d,
+                                     stride, out.stride(0), float(scale), *wa, _stream()), name)
     return dqkv
+
+
+def attn_bidir_bwd(qkv: torch.Tensor, key_bits: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, B: int, S: int,
+                   nq: int, nkv: int, d: int, dqkv: torch.Tensor | None = None, scale: float | None = None,
+                   causal: bool = False, window: int = 0) -> torch.Tensor:
+    return _attn_bwd("bwd", qkv, key_bits, "key_bits", (B, S), (B, nq, S), out, dout, lse, nq, nkv, d, dqkv, scale, causal, window)
 
 
 def attn_bidir_varlen_bwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, out: torch.Tensor, dout: torch.Tensor,
                           lse: torch.Tensor, nq: int, nkv: int, d: int, dqkv: torch.Tensor | None = None,
                           scale: float | None = None, causal: bool = False, window: int = 0) -> torch.Tensor:
-    T, stride = qkv.shape
-    B = cu_seqlens.numel() - 1
-    if dqkv is None:
-        dqkv = torch.empty_like(qkv)
-    if scale is None:
-        scale = d ** -0.5
-    delta = torch.empty((T, nq), dtype=F32, device=qkv.device)
-    fn, wa = _attn_entry("varlen_bwd", causal, window)
-    check(fn(_chk(qkv, BF16, "qkv"), _chk(cu_seqlens, I32, "cu_seqlens"), _chk(out, BF16, "out"), _chk(dout, BF16, "dout"), _chk(lse, F32, "lse"),
-             delta.data_ptr(), _chk(dqkv, BF16, "dqkv"), B, int(max_len), T, nq, nkv, d, stride, out.stride(0), float(scale), *wa, _stream()),
-          "grit_attn_bidir_varlen_bwd")
-    return dqkv
+    T = qkv.shape[0]
+    return _attn_bwd("varlen_bwd", qkv, cu_seqlens, "cu_seqlens", (cu_seqlens.numel() - 1, int(max_len), T), (T, nq), out, dout, lse, nq, nkv, d, dqkv,
+                     scale, causal, window)
 
 
 def _proj_args(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None, epilogue: int, ln_w: torch.Tensor | None = None, eps: float = 0.0):
