@@ -14,14 +14,11 @@
 // -- the stream's copy h16 in front of a norm, ctx, act -- is fp16, rounded once from fp32; K / V are rounded to fp16 once when they
 // enter the cache.  Values beyond the fp16 range raise the per-device flag word every fp16 kernel of the library reports through (common.h).
 #include "common.h"
+#include "decode_epi.h"
+#include "next_token.h"
 
 namespace grit {
 
-
-__device__ __forceinline__ float dot8(const uint4 a, const uint4 b) {
-  return bflo(a.x) * bflo(b.x) + bfhi(a.x) * bfhi(b.x) + bflo(a.y) * bflo(b.y) + bfhi(a.y) * bfhi(b.y) + bflo(a.z) * bflo(b.z) +
-         bfhi(a.z) * bfhi(b.z) + bflo(a.w) * bflo(b.w) + bfhi(a.w) * bfhi(b.w);
-}
 // eight 16-bit values of the operand format -> fp32
 template <bool F16>
 __device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
@@ -34,8 +31,6 @@ __device__ __forceinline__ uint32_t pack2_rne(float lo, float hi) {
   if constexpr (F16) return pack2h_hw(lo, hi);
   else return pack2bf(lo, hi);
 }
-// one fp32 value -> the 16 bits of its fp16 rounding (RNE; beyond 65504: inf, reported by the caller)
-__device__ __forceinline__ uint16_t f2h_bits(float f) { return (uint16_t)(pack2h_hw(f, 0.f) & 0xffffu); }
 
 // All-reduce of NG independent values over the 64 lanes in registers: four row rotations by DPP (all-reduce inside every 16-lane row),
 // then v_permlane16_swap / v_permlane32_swap for the rows (gfx950) -- no LDS-queue instruction.  (`wave_max` / `wave_sum` of common.h
@@ -66,15 +61,11 @@ __device__ __forceinline__ void wave_allreduce(float (&v)[NG]) {
   }
 }
 
-#ifndef GRIT_GV_ROWS
-#define GRIT_GV_ROWS 4      // (A/B builds: tools/decode_variants.sh)
-#endif
-constexpr int GV_ROWS = GRIT_GV_ROWS;  // weight rows per workgroup; its 4 waves each take a quarter of K (split-K, LDS reduce)
-#ifndef GRIT_GV_ROWS_SWIGLU
-#define GRIT_GV_ROWS_SWIGLU GRIT_GV_ROWS
-#endif
-constexpr int GV_ROWS_SW = GRIT_GV_ROWS_SWIGLU;   // the same for the gate|up launches (SwiGLU epilogue: rows come in (gate, up) pairs);
-                                                  // 4 / 8 / 16 rows: 2.757 / 2.798 / 2.824 ms per token (profiles/r06_decode_f16_ab.log)
+// weight rows per workgroup (SwiGLU: rows come in (gate, up) pairs) and its waves, each of which takes a quarter of K (split-K, LDS reduce).
+// Measured and rejected: 4 / 8 / 16 rows for the gate|up launches: 2.757 / 2.798 / 2.824 ms per token; workgroups of 8 waves where
+// K <= 4096 (one iteration per lane): 2.754 -> 2.747 ms per token on bf16, 2.766 -> 2.743 on fp16 operands: not the default
+// (profiles/r06_decode_f16_ab.log, blocks 2 and 4)
+constexpr int GV_ROWS = 4, GV_WAVES = 4;
 
 // MODE 0: store, 1: + residual, 2: SwiGLU pairs (rows r, r+16 of the interleaved layout).
 // PRENORM 1: x is the raw residual stream and the kernel applies MistralRMSNorm on the fly (x_n = bf16(w_ln * bf16(x * rsqrt(mean x^2 + eps))),
@@ -89,17 +80,18 @@ constexpr int GV_ROWS_SW = GRIT_GV_ROWS_SWIGLU;   // the same for the gate|up la
 // activation (one rounding of silu(g) * u).  MODE 1 additionally writes out16 = fp16(out): the operand copy of the stream the next
 // norm + GEMV reads (an fp32 x would double the x traffic of the 7168 gate|up workgroups: measured +2.8 us per launch, 3 % of a token).
 // PRENORM 1 (the exact bf16 form) has no fp16 counterpart.  ld* are in elements of the respective format.
-template <int NB, int MODE, int PRENORM, int R, bool F16 = false, int WV = 4>
-__global__ void __launch_bounds__(64 * WV) gemv_bf16_k(const uint16_t* __restrict__ x, const uint16_t* __restrict__ W, uint16_t* __restrict__ out,
-                                                   const uint16_t* __restrict__ res, const uint16_t* __restrict__ ln_w, float eps, int B, int N,
-                                                   int K, int64_t ldx, int64_t ldw, int64_t ldo, int64_t ldr, unsigned int* __restrict__ flag,
-                                                   uint16_t* __restrict__ out16, int64_t ldo16, const int32_t* __restrict__ widx, int64_t w_estride, int w_nexp) {
+template <int NB, int MODE, int PRENORM, bool F16 = false>
+__global__ void __launch_bounds__(64 * GV_WAVES) gemv_bf16_k(const uint16_t* __restrict__ x, const uint16_t* __restrict__ W, uint16_t* __restrict__ out,
+                                                         const uint16_t* __restrict__ res, const uint16_t* __restrict__ ln_w, float eps, int B, int N,
+                                                         int K, int64_t ldx, int64_t ldw, int64_t ldo, int64_t ldr, unsigned int* __restrict__ flag,
+                                                         uint16_t* __restrict__ out16, int64_t ldo16, const int32_t* __restrict__ widx, int64_t w_estride, int w_nexp) {
   static_assert(!(F16 && PRENORM == 1), "the exact fused norm rounds to bf16: bf16 only");
+  constexpr int R = GV_ROWS, WV = GV_WAVES;
   // widx (nullable): W is a stack of matrices [E, N, K] and this launch multiplies by matrix widx[0] -- the expert a sparse-MoE decode step
   // routed the row to, read from DEVICE memory so that the step stays one HIP graph.  The index is clamped to [0, w_nexp): whatever the
   // device word holds, the launch never reads outside the stack
   if (widx) W += (int64_t)max(0, min(widx[0], w_nexp - 1)) * w_estride;
-  __shared__ float red[WV][R][NB];                            // WV waves per workgroup, each takes 1 / WV of K (split-K, LDS reduce)
+  __shared__ float red[WV][R][NB];
   __shared__ float red_ss[WV][NB];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int unit = blockIdx.x;                                // one unit = R weight rows
@@ -127,10 +119,6 @@ __global__ void __launch_bounds__(64 * WV) gemv_bf16_k(const uint16_t* __restric
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
     const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(W + (int64_t)rows[i] * ldw) + c);
     return make_uint4(v[0], v[1], v[2], v[3]);
-  };
-  // eight x values of row b at chunk c, as fp32
-  auto xload = [&](int b, int c, float (&xf)[8]) {
-    unpack8<F16>(reinterpret_cast<const uint4*>(x + (int64_t)(b < B ? b : 0) * ldx)[c], xf);
   };
   const int c0 = wave * 64 + lane;
   uint4 wv[R];
@@ -171,53 +159,44 @@ __global__ void __launch_bounds__(64 * WV) gemv_bf16_k(const uint16_t* __restric
     if (PRENORM) lw = reinterpret_cast<const uint4*>(ln_w)[c];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-      if (PRENORM == 2 || F16) {
-        float xs[8];
-        xload(b, c, xs);
+      // eight x values of the row as fp32, the norm form applied (the norm weights stay bf16): PRENORM 1 rounds twice like the reference,
+      // PRENORM 2 multiplies by the norm weight only and collects the row's sum of squares.  (Written in line: behind a lambda hipcc
+      // contracted the bf16 sum of squares differently at 2, 4 and 8 rows per launch -- other fp32 bits in the row scale, which bf16
+      // outputs show only once in thousands of elements.)
+      float xs[8];
+      unpack8<F16>(reinterpret_cast<const uint4*>(x + (int64_t)(b < B ? b : 0) * ldx)[c], xs);
+      if constexpr (PRENORM != 0) {
+        float lf[8];
+        unpack8<false>(lw, lf);
+        if constexpr (PRENORM == 1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) xs[e] = round_bf(round_bf(xs[e] * inv[b]) * lf[e]);
+        } else if constexpr (F16) {                           // pinned like the fp16 product below
+#pragma clang fp contract(off)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { ssq[b] = __builtin_fmaf(xs[e], xs[e], ssq[b]); xs[e] = xs[e] * lf[e]; }
+        } else {                                              // (bf16: kept apart from the pinned form -- the contraction is the compiler's, as in the product)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { ssq[b] += xs[e] * xs[e]; xs[e] = xs[e] * lf[e]; }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        float wf[8];
+        unpack8<F16>(wv[i], wf);
         if constexpr (F16) {
           // The fp16-operand forms PIN their contraction (one product, then an fma chain): left to the compiler, the NB = 1 / 4 and the
           // NB = 2 / 8 instantiations of the deferred-norm form contracted differently and a row's bits depended on how many rows shared
           // the launch (tools/gemv_rows_probe.py) -- the prompt chunk (8 rows per launch) must reproduce the token-by-token prompt.
 #pragma clang fp contract(off)
-          if (PRENORM == 2) {
-            const float lf[8] = {bflo(lw.x), bfhi(lw.x), bflo(lw.y), bfhi(lw.y), bflo(lw.z), bfhi(lw.z), bflo(lw.w), bfhi(lw.w)};   // (norm weights stay bf16)
+          float t = wf[0] * xs[0];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { ssq[b] = __builtin_fmaf(xs[e], xs[e], ssq[b]); xs[e] = xs[e] * lf[e]; }
-          }
-#pragma unroll
-          for (int i = 0; i < R; ++i) {
-            float wf[8];
-            unpack8<true>(wv[i], wf);
-            float t = wf[0] * xs[0];
-#pragma unroll
-            for (int e = 1; e < 8; ++e) t = __builtin_fmaf(wf[e], xs[e], t);
-            acc[i][b] = acc[i][b] + t;
-          }
-          continue;
+          for (int e = 1; e < 8; ++e) t = __builtin_fmaf(wf[e], xs[e], t);
+          acc[i][b] = acc[i][b] + t;
+        } else {
+          acc[i][b] += wf[0] * xs[0] + wf[1] * xs[1] + wf[2] * xs[2] + wf[3] * xs[3] + wf[4] * xs[4] + wf[5] * xs[5] + wf[6] * xs[6] + wf[7] * xs[7];
         }
-        if (PRENORM == 2) {
-          const float lf[8] = {bflo(lw.x), bfhi(lw.x), bflo(lw.y), bfhi(lw.y), bflo(lw.z), bfhi(lw.z), bflo(lw.w), bfhi(lw.w)};   // (norm weights stay bf16)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { ssq[b] += xs[e] * xs[e]; xs[e] = xs[e] * lf[e]; }
-        }
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-          const uint4 w = wv[i];
-          acc[i][b] += lo16_op<F16>(w.x) * xs[0] + hi16_op<F16>(w.x) * xs[1] + lo16_op<F16>(w.y) * xs[2] + hi16_op<F16>(w.y) * xs[3] +
-                       lo16_op<F16>(w.z) * xs[4] + hi16_op<F16>(w.z) * xs[5] + lo16_op<F16>(w.w) * xs[6] + hi16_op<F16>(w.w) * xs[7];
-        }
-        continue;
       }
-      uint4 xv = reinterpret_cast<const uint4*>(x + (int64_t)(b < B ? b : 0) * ldx)[c];
-      if (PRENORM == 1) {
-        const float s_ = inv[b];
-        xv.x = pack2bf(round_bf(bflo(xv.x) * s_) * bflo(lw.x), round_bf(bfhi(xv.x) * s_) * bfhi(lw.x));
-        xv.y = pack2bf(round_bf(bflo(xv.y) * s_) * bflo(lw.y), round_bf(bfhi(xv.y) * s_) * bfhi(lw.y));
-        xv.z = pack2bf(round_bf(bflo(xv.z) * s_) * bflo(lw.z), round_bf(bfhi(xv.z) * s_) * bfhi(lw.z));
-        xv.w = pack2bf(round_bf(bflo(xv.w) * s_) * bflo(lw.w), round_bf(bfhi(xv.w) * s_) * bfhi(lw.w));
-      }
-#pragma unroll
-      for (int i = 0; i < R; ++i) acc[i][b] += dot8(wv[i], xv);
     }
   }
   // the wave's R x NB (+ NB) partial sums are reduced TOGETHER in registers (wave_allreduce: DPP row rotations + permlane swaps, the chains
@@ -246,55 +225,30 @@ __global__ void __launch_bounds__(64 * WV) gemv_bf16_k(const uint16_t* __restric
     }
   }
   __syncthreads();
-  // thread t < R*NB finishes output (row i, batch b)
+  // thread t finishes one output: (row i, batch b), under SwiGLU (pair i, batch b); the rounding points are decode_epi.h's
+  constexpr int OUTS = MODE == 2 ? R / 2 : R;
   const int t = threadIdx.x;
-  auto row_scale = [&](int b) -> float {
-    if (PRENORM != 2) return 1.0f;
+  if (t >= OUTS * NB) return;
+  const int i = t / NB, b = t - i * NB, n = unit * OUTS + i;
+  if (n >= (MODE == 2 ? N / 2 : N) || b >= B) return;
+  float rs = 1.0f;
+  if (PRENORM == 2) {
     float ss = red_ss[0][b];
 #pragma unroll
     for (int w = 1; w < WV; ++w) ss += red_ss[w][b];
-    return rsqrtf(ss / (float)K + eps);
-  };
-  auto total = [&](int i, int b) -> float {                   // the waves' partial sums, in wave order
-    float v = red[0][i][b];
-#pragma unroll
-    for (int w = 1; w < WV; ++w) v += red[w][i][b];
-    return v;
-  };
-  if (MODE == 2) {
-    if (t < (R / 2) * NB) {
-      const int i = t / NB, b = t - i * NB, p = unit * (R / 2) + i;
-      if (p < N / 2 && b < B) {
-        const float rs = row_scale(b);
-        const float g = total(2 * i, b) * rs;
-        const float u = total(2 * i + 1, b) * rs;
-        if constexpr (F16) {
-          const uint16_t hb = f2h_bits(silu_f(g) * u);
-          if ((hb & 0x7c00u) == 0x7c00u) atomicOr(flag, 1u);
-          out[(int64_t)b * ldo + p] = hb;
-        } else {
-          out[(int64_t)b * ldo + p] = (uint16_t)f2bf(round_bf(silu_f(round_bf(g))) * round_bf(u));
-        }
-      }
-    }
-  } else if (t < R * NB) {
-    const int i = t / NB, b = t - i * NB, n = unit * R + i;
-    if (n < N && b < B) {
-      float v = total(i, b) * row_scale(b);
-      if constexpr (F16) {
-        if (MODE == 1) v += reinterpret_cast<const float*>(res)[(int64_t)b * ldr + n];
-        reinterpret_cast<float*>(out)[(int64_t)b * ldo + n] = v;
-        if (MODE == 1 && out16) {
-          const uint16_t hb = f2h_bits(v);
-          if ((hb & 0x7c00u) == 0x7c00u) atomicOr(flag, 1u);
-          out16[(int64_t)b * ldo16 + n] = hb;
-        }
-      } else {
-        if (MODE == 1) v = round_bf(v) + bf2f(res[(int64_t)b * ldr + n]);
-        out[(int64_t)b * ldo + n] = (uint16_t)f2bf(v);
-      }
-    }
+    rs = rsqrtf(ss / (float)K + eps);
   }
+  auto total = [&](int row) -> float {                        // the waves' partial sums, in wave order
+    float v = red[0][row][b];
+#pragma unroll
+    for (int w = 1; w < WV; ++w) v += red[w][row][b];
+    return v * rs;
+  };
+  const float v = total(MODE == 2 ? 2 * i : i);
+  float r = 0.f;
+  if (MODE == 1) r = decode_epi_residual<F16>(res, (int64_t)b * ldr + n);
+  if (MODE == 2) r = total(2 * i + 1);
+  if (decode_epi<MODE, F16>(v, r, out, (int64_t)b * ldo + n, out16, (int64_t)b * ldo16 + n)) atomicOr(flag, 1u);
 }
 
 // ---- RoPE of the new token's q, k (at position lens[b]) + append of its k, v to the cache, one launch.
@@ -384,53 +338,49 @@ __global__ void __launch_bounds__(256) kv_append_k(const uint16_t* __restrict__ 
   }
 }
 
-// ---- decode attention, head_dim 128.  grid (splits of 64 keys, nkv, B), ONE wave per workgroup: at 1-8 sequences the work is tiny, what
-//      matters is that every 64-key slice of the cache is read by its own wave somewhere on the chip (2 k keys x 8 kv heads = 264 waves).
+// ---- decode attention, head_dim 128.  grid (splits of 64 keys, nq, B), ONE wave per workgroup: at 1-8 sequences the work is tiny, what
+//      matters is that every 64-key slice of the cache is read by its own wave somewhere on the chip.
 constexpr int AD_D = 128, AD_CH = 64, AD_G = 8;   // up to 8 query heads per kv head
-// ROPE: q arrives un-rotated in the fused qkv row; every workgroup rotates its G query heads itself (position lens[b]) and the one whose
-// slice contains that position also rotates the new k, appends k and v to the cache and then reads them back like any other key --
-// the RoPE + KV-append launch of a decode step disappears.
-// G = query heads per kv head, a TEMPLATE argument (round 5): with the run-time G of rounds 1-4 every loop over the heads carried an
-// `if (g >= G) break`, the compiler could neither unroll nor interleave the heads' dot products and reductions, and the one wave of a
-// workgroup executed them back to back -- the kernel was bound by its own dependent-instruction chains (11.4 us per layer at L = 2 k
-// for 32 KB of K / V per workgroup), not by memory.
-// PH ("per head", G = 1): one workgroup per QUERY head instead of per kv head -- blockIdx.y is the query head, the gq heads of a kv group
-// are gq workgroups that read the same K / V slice (the duplicates hit L2) and each does a quarter of the arithmetic: the kernel is one
-// wave deep and bound by its own instruction stream (a slice of 64 keys x 4 heads is ~2000 dependent-free FMAs per lane), not by the
-// 32 KB it reads.  Every one of them rotates the new key itself; they write identical cache rows.
+// One workgroup per (split, QUERY head, row): the gq = nq / nkv heads of a kv group are gq workgroups that read the same K / V slice and
+// each does its own head's arithmetic (MHA: one head per group).  The kernel is one wave deep and bound by its own dependent-instruction
+// chains (a slice of 64 keys x 4 heads is ~2000 FMAs per lane), not by the 32 KB it reads, and the duplicate K / V reads of a group hit
+// L2: a workgroup per kv head that worked through its group's heads was slower, 8.74 -> 7.52 us per launch at L = 2 k, 32 / 8 heads
+// (kernel trace, profiles/r05_decode_kernel_stats_perhead.csv).
+// ROPE: q arrives un-rotated in the fused qkv row; every workgroup rotates its query head itself (position lens[b]) and the ones whose
+// slice contains that position also rotate the new k, append k and v to the cache (the heads of a group write identical cache rows) and
+// then read them back like any other key -- the RoPE + KV-append launch of a decode step disappears.
 // F16: the q (ROPE: q|k|v) row is fp32 -- q is rotated and scaled without a rounding, the new k / v are rounded to fp16 once, on their way
 // into the cache -- and the cache is fp16.
-template <bool ROPE, int G, bool PH = false, bool F16 = false>
+template <bool ROPE, bool F16 = false>
 __global__ void __launch_bounds__(64) attn_decode_k(const uint16_t* __restrict__ q, uint16_t* __restrict__ ck, uint16_t* __restrict__ cv,
                                                     const int32_t* __restrict__ lens, float* __restrict__ part, const float* __restrict__ cos_tab,
                                                     const float* __restrict__ sin_tab, int nq, int nkv, int Lmax, int64_t q_stride, float scale,
                                                     int max_splits, unsigned int* __restrict__ flag, const int32_t* __restrict__ cache_row) {
-  __shared__ __attribute__((aligned(16))) float qs[G][AD_D];   // query heads of this kv head, pre-scaled
-  __shared__ float ps[G][64];                                  // probabilities of the 64 keys
+  __shared__ __attribute__((aligned(16))) float qs[AD_D];      // the query head, pre-scaled
+  __shared__ float ps[64];                                     // probabilities of the 64 keys
   __shared__ __attribute__((aligned(16))) uint16_t newk[AD_D]; // ROPE, owner workgroup: the new key (rotated) and value rows, handed to the
   __shared__ __attribute__((aligned(16))) uint32_t newv[AD_D / 2];   // lanes that hold them in the K / V register layouts
-  const int gq = PH ? nq / nkv : G;                       // query heads per kv head in the q row / the partials' layout
-  const int split = blockIdx.x, hk = PH ? (int)blockIdx.y / gq : (int)blockIdx.y, b = blockIdx.z;
-  const int g0 = PH ? (int)blockIdx.y - hk * gq : 0;      // this workgroup's first (PH: only) head inside the group
+  const int gq = nq / nkv;                                // query heads per kv head in the q row / the partials' layout
+  const int split = blockIdx.x, hq = blockIdx.y, hk = hq / gq, b = blockIdx.z;
   const int lane = threadIdx.x;
   const int cb = cache_row ? cache_row[b] : b;   // the sequence whose cache row b attends to (several rows may be tokens of one sequence)
   const int L = lens[b] + 1;                 // keys 0 .. lens[b] (the new token was appended)
   const int k0 = split * AD_CH;
-  float* pbase = part + ((((int64_t)b * nkv + hk) * max_splits + split) * gq + g0) * (AD_D + 2);
+  float* pbase = part + ((((int64_t)b * nkv + hk) * max_splits + split) * gq + (hq - hk * gq)) * (AD_D + 2);
   if (k0 >= L) {                             // empty split: neutral element
-    for (int i = lane; i < G * (AD_D + 2); i += 64) pbase[i] = (i % (AD_D + 2) == 0) ? -INFINITY : 0.f;
+    for (int i = lane; i < AD_D + 2; i += 64) pbase[i] = i == 0 ? -INFINITY : 0.f;
     return;
   }
-  // The slice's K and V rows are requested FIRST: 32 independent 16-byte loads per lane go out before the query heads are fetched,
-  // rotated and staged -- also in the one workgroup whose slice receives the NEW key (round 5: it used to append first and load
-  // afterwards, two memory latencies in a row on the kernel's critical path): its loads of the new key's cache row return whatever the
+  // The slice's K and V rows are requested FIRST: 32 independent 16-byte loads per lane go out before the query head is fetched,
+  // rotated and staged -- also in the workgroups whose slice receives the NEW key (round 5: they used to append first and load
+  // afterwards, two memory latencies in a row on the kernel's critical path): their loads of the new key's cache row return whatever the
   // slot held, and the rotated k / the v row replace those registers through LDS after the barrier.
   const int key = k0 + lane;
   const bool live = key < L;
   const int kg = lane >> 4, dc = lane & 15;                  // PV layout: key group kg (16 keys), dim chunk dc (8 dims)
   const int nk = min(64, L - k0);
   uint4 kreg[AD_D / 8], vreg[16];
-  auto load_kv = [&]() {
+  {
     const uint4* kr = reinterpret_cast<const uint4*>(ck + (((int64_t)cb * nkv + hk) * Lmax + (live ? key : L - 1)) * AD_D);
 #pragma unroll
     for (int c = 0; c < AD_D / 8; ++c) kreg[c] = kr[c];       // 16 independent loads in flight
@@ -440,28 +390,20 @@ __global__ void __launch_bounds__(64) attn_decode_k(const uint16_t* __restrict__
       const int kk = kg * 16 + j;
       vreg[j] = reinterpret_cast<const uint4*>(vbase + (int64_t)(kk < nk ? kk : nk - 1) * AD_D)[dc];
     }
-  };
+  }
   const bool owner = ROPE && (L - 1 >= k0) && (L - 1 < k0 + AD_CH);      // workgroup-uniform
-  load_kv();
   if constexpr (ROPE) {
     const int pos = L - 1;
     const float c = cos_tab[(int64_t)pos * 64 + lane], sn = sin_tab[(int64_t)pos * 64 + lane];     // lane <-> pair (e, e + 64)
     const uint16_t* row = q + (int64_t)b * q_stride;
     const float* rowf = reinterpret_cast<const float*>(q) + (int64_t)b * q_stride;       // F16: the fp32 q|k|v row
     auto qk_at = [&](int64_t i) -> float { if constexpr (F16) return rowf[i]; else return bf2f(row[i]); };
-    float x1[G], x2[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {                             // all 2 G loads in flight before the first use
-      x1[g] = qk_at((int64_t)(hk * gq + g0 + g) * AD_D + lane); x2[g] = qk_at((int64_t)(hk * gq + g0 + g) * AD_D + 64 + lane);
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      if constexpr (F16) {
-        qs[g][lane] = rope_lo(x1[g], x2[g], c, sn) * scale; qs[g][64 + lane] = rope_hi(x1[g], x2[g], c, sn) * scale;
-      } else {
-        const uint32_t r = pack2bf(rope_lo(x1[g], x2[g], c, sn), rope_hi(x1[g], x2[g], c, sn));         // one rounding, as rope_k
-        qs[g][lane] = bflo(r) * scale; qs[g][64 + lane] = bfhi(r) * scale;
-      }
+    const float x1 = qk_at((int64_t)hq * AD_D + lane), x2 = qk_at((int64_t)hq * AD_D + 64 + lane);
+    if constexpr (F16) {
+      qs[lane] = rope_lo(x1, x2, c, sn) * scale; qs[64 + lane] = rope_hi(x1, x2, c, sn) * scale;
+    } else {
+      const uint32_t r = pack2bf(rope_lo(x1, x2, c, sn), rope_hi(x1, x2, c, sn));         // one rounding, as rope_k
+      qs[lane] = bflo(r) * scale; qs[64 + lane] = bfhi(r) * scale;
     }
     if (owner) {                                          // this workgroup owns the new key: rotate k, append k and v
       const int64_t ko = (int64_t)(nq + hk) * AD_D, vo = (int64_t)(nq + nkv + hk) * AD_D;
@@ -481,10 +423,9 @@ __global__ void __launch_bounds__(64) attn_decode_k(const uint16_t* __restrict__
       newv[lane] = vw;
     }
   } else {
-    for (int i = lane; i < G * AD_D; i += 64) {
-      const int g = i / AD_D, e = i - g * AD_D;
-      const int64_t qi = (int64_t)b * q_stride + (int64_t)(hk * gq + g0 + g) * AD_D + e;
-      qs[g][e] = (F16 ? reinterpret_cast<const float*>(q)[qi] : bf2f(q[qi])) * scale;
+    for (int e = lane; e < AD_D; e += 64) {
+      const int64_t qi = (int64_t)b * q_stride + (int64_t)hq * AD_D + e;
+      qs[e] = (F16 ? reinterpret_cast<const float*>(q)[qi] : bf2f(q[qi])) * scale;
     }
   }
   __syncthreads();
@@ -499,65 +440,46 @@ __global__ void __launch_bounds__(64) attn_decode_k(const uint16_t* __restrict__
     for (int j = 0; j < 16; ++j)                               // the new key is the slice's last one: every clamped row index (keys past
       if (kg * 16 + j >= lk) vreg[j] = nv;                     // the sequence, probability 0) pointed at its slot as well
   }
-  float s[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) s[g] = 0.f;
+  float s = 0.f;
 #pragma unroll
   for (int c = 0; c < AD_D / 8; ++c) {
     float kf[8];
     unpack8<F16>(kreg[c], kf);
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float4 qa = *reinterpret_cast<const float4*>(&qs[g][c * 8]), qb = *reinterpret_cast<const float4*>(&qs[g][c * 8 + 4]);
-      s[g] += kf[0] * qa.x + kf[1] * qa.y + kf[2] * qa.z + kf[3] * qa.w + kf[4] * qb.x + kf[5] * qb.y + kf[6] * qb.z + kf[7] * qb.w;
-    }
+    const float4 qa = *reinterpret_cast<const float4*>(&qs[c * 8]), qb = *reinterpret_cast<const float4*>(&qs[c * 8 + 4]);
+    s += kf[0] * qa.x + kf[1] * qa.y + kf[2] * qa.z + kf[3] * qa.w + kf[4] * qb.x + kf[5] * qb.y + kf[6] * qb.z + kf[7] * qb.w;
   }
-  float mg[G], lg[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) mg[g] = live ? s[g] : -INFINITY;
-  wave_allreduce<G, true>(mg);
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const float p = live ? __expf(s[g] - mg[g]) : 0.f;
-    lg[g] = p;
-    ps[g][lane] = p;
-  }
-  wave_allreduce<G, false>(lg);
+  float m[1] = {live ? s : -INFINITY};
+  wave_allreduce<1, true>(m);
+  const float p = live ? __expf(s - m[0]) : 0.f;
+  float l[1] = {p};
+  ps[lane] = p;
+  wave_allreduce<1, false>(l);
   __syncthreads();
   // O partial: lane = (key group kg = lane>>4, dim chunk dc = lane&15): 16 INDEPENDENT 16-byte loads per lane (keys kg*16 .. +15, dims
   // 8dc .. +7; requested at the top of the kernel), then the 4 key groups are folded through the two row swaps
-  float o[G][8];
+  float o[8];
 #pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     float vf[8];
     unpack8<F16>(vreg[j], vf);
+    const float pj = ps[kg * 16 + j];                // 0 for keys past the sequence
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float p = ps[g][kg * 16 + j];            // 0 for keys past the sequence
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[g][e] += p * vf[e];
-    }
+    for (int e = 0; e < 8; ++e) o[e] += pj * vf[e];
   }
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {                    // fold the four key groups (rows of 16 lanes): same dims sit 16 / 32 lanes apart
-      const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(o[g][e]), __float_as_uint(o[g][e]), false, false);
-      const float t = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-      const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(t), __float_as_uint(t), false, false);
-      o[g][e] = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
-    }
-    float* pg = pbase + g * (AD_D + 2);
-    if (kg == 0) {
-      *reinterpret_cast<float4*>(pg + 2 + 8 * dc) = make_float4(o[g][0], o[g][1], o[g][2], o[g][3]);
-      *reinterpret_cast<float4*>(pg + 2 + 8 * dc + 4) = make_float4(o[g][4], o[g][5], o[g][6], o[g][7]);
-    }
-    if (lane == 0) { pg[0] = mg[g]; pg[1] = lg[g]; }
+  for (int e = 0; e < 8; ++e) {                      // fold the four key groups (rows of 16 lanes): same dims sit 16 / 32 lanes apart
+    const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(o[e]), __float_as_uint(o[e]), false, false);
+    const float t = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
+    const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(t), __float_as_uint(t), false, false);
+    o[e] = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
   }
+  if (kg == 0) {
+    *reinterpret_cast<float4*>(pbase + 2 + 8 * dc) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(pbase + 2 + 8 * dc + 4) = make_float4(o[4], o[5], o[6], o[7]);
+  }
+  if (lane == 0) { pbase[0] = m[0]; pbase[1] = l[0]; }
 }
 
 template <bool F16 = false>
@@ -608,53 +530,35 @@ __global__ void __launch_bounds__(128) attn_decode_combine_k(const float* __rest
 }
 
 // ---- greedy sampling + advance: next[b] = argmax_v logits[b, v] (lowest index on ties), lens[b] += 1
-// L32: fp32 logits (the fp16-operand decode step keeps them unrounded)
+// L32: fp32 logits (the fp16-operand decode step keeps them unrounded).  NaN never wins.
 template <bool L32 = false>
 __global__ void __launch_bounds__(256) argmax_advance_k(const uint16_t* __restrict__ logits, int64_t ld, int V, int64_t* __restrict__ next,
                                                         int32_t* __restrict__ lens, int64_t* __restrict__ history, int64_t hist_stride,
                                                         const int32_t* __restrict__ step) {
   __shared__ float bv[4];
   __shared__ int bi[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   float best = -INFINITY;
   int idx = 0x7fffffff;
-  const uint16_t* row = logits + (int64_t)b * ld;
-  const float* rowf = reinterpret_cast<const float*>(logits) + (int64_t)b * ld;
-  const int VC = V >> 3;                                      // chunks of 8 (ld % 8 == 0 keeps the rows aligned)
+  const void* row = L32 ? (const void*)(reinterpret_cast<const float*>(logits) + (int64_t)b * ld) : (const void*)(logits + (int64_t)b * ld);
+  const int VC = V >> 3;                                      // full chunks of 8 (ld % 8 == 0 keeps the rows aligned)
   for (int c = tid; c < VC; c += 256) {
     float x[8];
-    if constexpr (L32) {
-      const float4 u = reinterpret_cast<const float4*>(rowf)[2 * c], w = reinterpret_cast<const float4*>(rowf)[2 * c + 1];
-      x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = w.x; x[5] = w.y; x[6] = w.z; x[7] = w.w;
-    } else {
-      unpack8<false>(reinterpret_cast<const uint4*>(row)[c], x);
-    }
+    load8_full<L32>(row, c, x);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       if (x[e] > best) { best = x[e]; idx = c * 8 + e; }      // ascending index inside a thread: first maximum wins
   }
-  for (int v = (VC << 3) + tid; v < V; v += 256) {
-    const float x = L32 ? rowf[v] : bf2f(row[v]);
-    if (x > best || (x == best && v < idx)) { best = x; idx = v; }
-  }
+  if ((V & 7) && tid == (VC & 255)) {                         // the row's partial last chunk (here a column of -inf takes the place of "no index")
+    float x[8];
+    load8_logits<L32>(row, VC, V, x);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+    for (int e = 0; e < 8; ++e)
+      if (VC * 8 + e < V) take_better(best, idx, x[e], VC * 8 + e);
   }
-  if (lane == 0) { bv[wave] = best; bi[wave] = idx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-    next[b] = idx;
-    if (history) history[(int64_t)b * hist_stride + step[0]] = idx;
-    if (lens) lens[b] += 1;
-  }
+  block_best<4>(best, idx, bv, bi, tid);
+  if (tid == 0) commit_token(b, idx, next, lens, history, hist_stride, step);
 }
-
-__global__ void bump_k(int32_t* v) { v[0] += 1; }
 
 // Sparse-MoE decode on fp16 operands: h[b] += w[b,0] y[2b] + w[b,1] y[2b+1] in fp32 (y: the two chosen experts' fp32 outputs of row b) and
 // h16 = fp16(h), the operand copy the next norm + GEMV reads -- one launch for the four elementwise passes a host-side combine would take.
@@ -677,62 +581,48 @@ __global__ void __launch_bounds__(256) moe_decode_combine_f32_k(float* __restric
 
 using namespace grit;
 
-template <int MODE, int PRENORM, bool F16 = false, int R = (MODE == 2 ? GV_ROWS_SW : GV_ROWS)>
-static int launch_gemv(const void* x, const void* W, void* out, const void* res, const void* ln_w, float eps, int B, int N, int K, int64_t ldx,
-                       int64_t ldw, int64_t ldo, int64_t ldr, hipStream_t st, void* out16 = nullptr, int64_t ldo16 = 0,
-                       const int32_t* widx = nullptr, int64_t w_estride = 0, int w_nexp = 0) {
-  const int units = MODE == 2 ? (N / 2 + R / 2 - 1) / (R / 2) : (N + R - 1) / R;
-  const dim3 grid((unsigned)units);
-  unsigned int* flag = F16 ? f16_flag_ptr() : nullptr;
-  if (F16 && !flag) return GRIT_E_LAUNCH;
-#define GRIT_GEMV_W(NB_, WV_)                                                                                                             \
-  hipLaunchKernelGGL((gemv_bf16_k<NB_, MODE, PRENORM, R, F16, WV_>), grid, dim3(64 * WV_), 0, st, (const uint16_t*)x, (const uint16_t*)W,       \
+template <int MODE, int PRENORM, bool F16>
+static int launch_gemv(const char* name, const void* x, const void* W, void* out, const void* res, const void* ln_w, float eps, int B, int N, int K,
+                       int64_t ldx, int64_t ldw, int64_t ldo, int64_t ldr, void* out16, int64_t ldo16, hipStream_t st, const int32_t* widx,
+                       int64_t w_estride, int w_nexp) {
+  constexpr int per = MODE == 2 ? GV_ROWS / 2 : GV_ROWS;      // outputs per workgroup (SwiGLU: pairs of rows)
+  const dim3 grid((unsigned)(((MODE == 2 ? N / 2 : N) + per - 1) / per));
+  unsigned int* flag;
+  if (const int rc = decode_proj_flag<F16>(name, &flag)) return rc;
+#define GRIT_GEMV(NB_)                                                                                                                    \
+  hipLaunchKernelGGL((gemv_bf16_k<NB_, MODE, PRENORM, F16>), grid, dim3(64 * GV_WAVES), 0, st, (const uint16_t*)x, (const uint16_t*)W,     \
                      (uint16_t*)out, (const uint16_t*)res, (const uint16_t*)ln_w, eps, B, N, K, ldx, ldw, ldo, ldr, flag, (uint16_t*)out16, ldo16,   \
                      widx, w_estride, w_nexp)
-  // GRIT_GV_WAVES_SHORT_K (A/B builds): workgroups of 8 waves where K <= 4096 (q|k|v, o_proj: every lane then covers its share of the row in
-  // ONE iteration -- one memory latency instead of two -- at twice the requests in flight per workgroup); 1- and 2-row steps only.
-  // Measured (profiles/r06_decode_f16_ab.log, block 4): 2.754 -> 2.747 ms per token on bf16, 2.766 -> 2.743 on fp16 operands: not the default.
-#ifdef GRIT_GV_WAVES_SHORT_K
-#define GRIT_GEMV(NB_) do { if (K <= 4096 && NB_ <= 2 && PRENORM != 1) GRIT_GEMV_W(NB_, GRIT_GV_WAVES_SHORT_K); else GRIT_GEMV_W(NB_, 4); } while (0)
-#else
-#define GRIT_GEMV(NB_) GRIT_GEMV_W(NB_, 4)
-#endif
   if (B == 1) GRIT_GEMV(1); else if (B == 2) GRIT_GEMV(2); else if (B <= 4) GRIT_GEMV(4); else GRIT_GEMV(8);
 #undef GRIT_GEMV
-#undef GRIT_GEMV_W
   GRIT_CHECK_LAUNCH(F16 ? "grit_gemv_f16" : "grit_gemv_bf16");
   return GRIT_OK;
 }
 
-// a STORE / SWIGLU launch by the norm in front of it: pn 0 none, 1 the exact fused norm (bf16 operands only), 2 the deferred one
-template <int MODE, bool F16, class... Args>
-static int launch_gemv_norm(int pn, Args... args) {
-  if constexpr (!F16) {
-    if (pn == 1) return launch_gemv<MODE, 1>(args...);
-  }
-  return pn == 2 ? launch_gemv<MODE, 2, F16>(args...) : launch_gemv<MODE, 0, F16>(args...);
-}
-
-// the epilogue's own checks and its launch, behind the other checks of an entry point (F16: the fp16-operand forms, formats in the
-// kernel's header comment; widx ...: the expert stack of grit_gemv_*_expert)
+// the epilogue's own checks and its launch, behind the other checks of an entry point (F16: the fp16-operand forms, formats in
+// decode_epi.h; pn: the norm in front -- 0 none, 1 the exact fused norm (bf16 operands only), 2 the deferred one; widx ...: the expert
+// stack of grit_gemv_*_expert)
+// (rows per workgroup of the RESIDUAL launches -- o_proj, down: N = 4096 -> 1024 workgroups of 4 rows, half a workgroup wave -- and the
+//  number of K-loop pieces a lane keeps in flight were A/B'd on one box: 1 / 2 / 4 rows 2.914 / 2.902 / 2.903 ms per token; 2 / 4
+//  pieces in flight 2.963 / 3.139 against 2.921 -- more requests in flight are SLOWER; profiles/r05_decode_{rows,unroll}_ab.log)
 template <bool F16>
 static int gemv_epilogue(const char* name, int epilogue, int pn, const void* x, const void* W, void* out, const void* ln_w, float eps, int B, int N,
                          int K, int64_t ldx, int64_t ldw, int64_t ldo, const void* residual, int64_t ldr, void* out16, int64_t ldo16,
                          hipStream_t st, const int32_t* widx = nullptr, int64_t w_estride = 0, int w_nexp = 0) {
-  switch (epilogue) {
-    case GRIT_EPI_STORE: GRIT_REQUIRE(ldo >= N, GRIT_E_BADARG, "%s: ldo < N", name);
-      return launch_gemv_norm<0, F16>(pn, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, widx, w_estride, w_nexp);
-    case GRIT_EPI_RESIDUAL: GRIT_REQUIRE(residual && ldo >= N && ldr >= N && !pn, GRIT_E_BADARG, "%s: RESIDUAL needs residual, ldo, ldr >= N (no pre-norm)", name);
-      GRIT_REQUIRE(!out16 || ldo16 >= N, GRIT_E_BADARG, "%s: ldo16 < N", name);
-      // (rows per workgroup of these launches -- o_proj, down: N = 4096 -> 1024 workgroups of 4 rows, half a workgroup wave -- and the
-      //  number of K-loop pieces a lane keeps in flight were A/B'd on one box: 1 / 2 / 4 rows 2.914 / 2.902 / 2.903 ms per token; 2 / 4
-      //  pieces in flight 2.963 / 3.139 against 2.921 -- more requests in flight are SLOWER; profiles/r05_decode_{rows,unroll}_ab.log)
-      return launch_gemv<1, 0, F16>(x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, st, out16, ldo16);
-    case GRIT_EPI_SWIGLU: GRIT_REQUIRE(N % 32 == 0 && ldo >= N / 2, GRIT_E_UNSUPPORTED, "%s: SWIGLU needs N %% 32 == 0, ldo >= N/2", name);
-      return launch_gemv_norm<2, F16>(pn, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, st, nullptr, 0, widx, w_estride, w_nexp);
-    default: GRIT_REQUIRE(false, GRIT_E_BADARG, "%s: unknown epilogue %d", name, epilogue);
-  }
-  return GRIT_OK;
+  return decode_proj_epilogue(name, epilogue, pn != 0, N, ldo, residual, ldr, out16, ldo16, [&](auto mode) -> int {
+    constexpr int MODE = decltype(mode)::value;
+    auto run = [&](auto norm) {
+      return launch_gemv<MODE, decltype(norm)::value, F16>(name, x, W, out, residual, ln_w, eps, B, N, K, ldx, ldw, ldo, ldr, out16, ldo16, st, widx,
+                                                            w_estride, w_nexp);
+    };
+    if constexpr (MODE != 1) {                                // (RESIDUAL takes no norm: refused above)
+      if constexpr (!F16) {
+        if (pn == 1) return run(std::integral_constant<int, 1>{});
+      }
+      if (pn == 2) return run(std::integral_constant<int, 2>{});
+    }
+    return run(std::integral_constant<int, 0>{});
+  });
 }
 
 // ln_w: the norm in front (fp16 operands: the deferred form only)
@@ -741,10 +631,10 @@ static int gemv_entry(const char* name, const void* x, const void* W, void* out,
                       int64_t ldw, int64_t ldo, int epilogue, const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream,
                       bool deferred = F16) {
   if (B == 0) return GRIT_OK;
-  GRIT_REQUIRE(x && W && out, GRIT_E_BADARG, "%s: null pointer", name);
+  if (const int rc = decode_proj_pointers(name, x, W, out)) return rc;
   GRIT_REQUIRE(B > 0 && B <= 8, GRIT_E_UNSUPPORTED, "%s: B=%d rows (1..8; larger batches use grit_gemm_%s_nt)", name, B, F16 ? "f16" : "bf16");
   GRIT_REQUIRE(N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldx >= K && ldw >= K, GRIT_E_BADARG, "%s: bad sizes", name);
-  GRIT_REQUIRE(aligned16(x) && aligned16(W) && (!ln_w || aligned16(ln_w)), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", name);
+  if (const int rc = decode_proj_aligned(name, x, W, ln_w)) return rc;
   return gemv_epilogue<F16>(name, epilogue, !ln_w ? 0 : deferred ? 2 : 1, x, W, out, ln_w, eps, B, N, K, ldx, ldw, ldo, residual, ldr, out16, ldo16,
                             (hipStream_t)stream);
 }
@@ -877,36 +767,14 @@ static int attn_decode_launch(const char* name, const void* q, void* cache_k, vo
   GRIT_REQUIRE(Lmax <= 512 * AD_CH, GRIT_E_UNSUPPORTED, "%s: Lmax=%d > %d", name, Lmax, 512 * AD_CH);
   const int splits = (Lmax + AD_CH - 1) / AD_CH;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)splits, (unsigned)nkv, (unsigned)B);
+  const dim3 grid((unsigned)splits, (unsigned)nq, (unsigned)B);
   unsigned int* flag = F16 ? f16_flag_ptr() : nullptr;
   if (F16 && !flag) return GRIT_E_LAUNCH;
-  // one workgroup per query head (PH above) for GQA models: 8.74 -> 7.52 us per launch at L = 2 k, 32 / 8 heads (kernel trace,
-  // profiles/r05_decode_kernel_stats_perhead.csv); GRIT_ATTN_DECODE_PER_HEAD=0 is the A/B knob
-  static const int per_head = getenv("GRIT_ATTN_DECODE_PER_HEAD") ? atoi(getenv("GRIT_ATTN_DECODE_PER_HEAD")) : 1;
-  if (per_head && nq / nkv > 1) {
-    const dim3 gridh((unsigned)splits, (unsigned)nq, (unsigned)B);
-    if (cos_tab)
-      hipLaunchKernelGGL((attn_decode_k<true, 1, true, F16>), gridh, dim3(64), 0, st, (const uint16_t*)q, (uint16_t*)cache_k, (uint16_t*)cache_v, lens, workspace,
-                         cos_tab, sin_tab, nq, nkv, Lmax, q_stride, scale, splits, flag, cache_row);
-    else
-      hipLaunchKernelGGL((attn_decode_k<false, 1, true, F16>), gridh, dim3(64), 0, st, (const uint16_t*)q, (uint16_t*)cache_k, (uint16_t*)cache_v, lens, workspace,
-                         cos_tab, sin_tab, nq, nkv, Lmax, q_stride, scale, splits, flag, cache_row);
-  } else {
-#define GRIT_AD_LAUNCH(R, GG)                                                                                                           \
-  hipLaunchKernelGGL((attn_decode_k<R, GG, false, F16>), grid, dim3(64), 0, st, (const uint16_t*)q, (uint16_t*)cache_k, (uint16_t*)cache_v, lens, workspace, \
-                     cos_tab, sin_tab, nq, nkv, Lmax, q_stride, scale, splits, flag, cache_row)
-#define GRIT_AD_BY_G(R)                                                                                                                 \
-  switch (nq / nkv) {                                                                                                                   \
-    case 1: GRIT_AD_LAUNCH(R, 1); break;                                                                                                \
-    case 2: GRIT_AD_LAUNCH(R, 2); break;                                                                                                \
-    case 4: GRIT_AD_LAUNCH(R, 4); break;                                                                                                \
-    case 8: GRIT_AD_LAUNCH(R, 8); break;                                                                                                \
-    default: GRIT_REQUIRE(false, GRIT_E_UNSUPPORTED, "%s: %d query heads per kv head (1, 2, 4 or 8 are built)", name, nq / nkv);       \
-  }
-  if (cos_tab) { GRIT_AD_BY_G(true) } else { GRIT_AD_BY_G(false) }
-#undef GRIT_AD_BY_G
-#undef GRIT_AD_LAUNCH
-  }
+  auto launch = [&](auto rope) {
+    hipLaunchKernelGGL((attn_decode_k<decltype(rope)::value, F16>), grid, dim3(64), 0, st, (const uint16_t*)q, (uint16_t*)cache_k, (uint16_t*)cache_v, lens,
+                       workspace, cos_tab, sin_tab, nq, nkv, Lmax, q_stride, scale, splits, flag, cache_row);
+  };
+  if (cos_tab) launch(std::true_type{}); else launch(std::false_type{});
   GRIT_CHECK_LAUNCH(name);
   hipLaunchKernelGGL(attn_decode_combine_k<F16>, dim3((unsigned)nq, (unsigned)B), dim3(AD_D), 0, st, (const float*)workspace, (uint16_t*)out, nq, nkv,
                      splits, out_stride);
@@ -955,17 +823,10 @@ template <bool L32>
 static int argmax_launch(const char* name, const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history, int64_t hist_stride,
                          int32_t* step, int B, void* stream) {
   if (B == 0) return GRIT_OK;
-  GRIT_REQUIRE(logits && next, GRIT_E_BADARG, "%s: null pointer", name);
-  GRIT_REQUIRE(V > 0 && ld >= V && ld % 8 == 0 && B > 0 && (!history || step), GRIT_E_BADARG, "%s: bad sizes", name);
-  GRIT_REQUIRE(aligned16(logits), GRIT_E_BADARG, "%s: logits must be 16-byte aligned", name);
+  if (const int rc = next_token_check(name, logits && next, logits, ld, V, history, step, B)) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(argmax_advance_k<L32>, dim3((unsigned)B), dim3(256), 0, st, (const uint16_t*)logits, ld, V, next, lens, history, hist_stride, step);
-  GRIT_CHECK_LAUNCH(name);
-  if (step) {
-    hipLaunchKernelGGL(bump_k, dim3(1), dim3(1), 0, st, step);
-    GRIT_CHECK_LAUNCH(name);
-  }
-  return GRIT_OK;
+  return next_token_finish(name, step, st);
 }
 
 extern "C" int grit_argmax_advance(const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history, int64_t hist_stride,

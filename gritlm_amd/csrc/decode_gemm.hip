@@ -26,9 +26,7 @@
 // (include/gritlm_hip.h).  The deferred norm accumulates the row's sum of squares from the x fragments the waves load for the product
 // (every x element is loaded by exactly one lane of one wave) and multiplies the finished sums by rsqrt(mean x^2 + eps); the MFMA needs a
 // 16-bit operand, so x * ln_weight is rounded ONCE to the operand format (the GEMV keeps it in fp32).
-#include "common.h"
-
-#include <type_traits>
+#include "decode_epi.h"
 
 namespace grit {
 
@@ -164,52 +162,25 @@ __global__ void __launch_bounds__(64 * WV) decode_gemm_k(const uint16_t* __restr
       for (int w = 1; w < WV; ++w) v += red[w][mb][ntile][l];
       return v * rs;
     };
+    // this thread's four elements (decode_epi.h holds the rounding points): RESIDUAL reads all four residual elements before it writes
+    // the first (out may be the residual: in place)
     const int q4 = 4 * (l >> 4);
+    const int64_t n = n0 + nt * 16 + q4;
+    const f32x4_t v = total(nt);
+    f32x4_t r = v;                                            // SWIGLU: the up sums; RESIDUAL: the residual; STORE: unused
+    int64_t o = (int64_t)b * ldo + n;
     if (MODE == 2) {
-      const f32x4_t gt = total(0), up = total(1 % NT);
-      const int64_t p = n0 / 2 + q4;                          // pair p: gate row (p / 16) * 32 + p % 16, up row + 16
-      uint16_t* o = reinterpret_cast<uint16_t*>(out) + (int64_t)b * ldo + p;
-      uint32_t ob = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (F16) {
-          const uint32_t hb = pack2h_hw(silu_f(gt[i]) * up[i], 0.f) & 0xffffu;
-          ob |= h2_nonfinite(hb);
-          o[i] = (uint16_t)hb;
-        } else {
-          o[i] = (uint16_t)f2bf(round_bf(silu_f(round_bf(gt[i]))) * round_bf(up[i]));
-        }
-      }
-      if (F16 && ob) atomicOr(flag, 1u);
-    } else {
-      f32x4_t v = total(nt);
-      const int64_t n = n0 + nt * 16 + q4;
-      if constexpr (F16) {
-        float* o = reinterpret_cast<float*>(out) + (int64_t)b * ldo + n;
-        if (MODE == 1) {
-          const float* rr = reinterpret_cast<const float*>(res) + (int64_t)b * ldr + n;
-          const float r0 = rr[0], r1 = rr[1], r2 = rr[2], r3 = rr[3];   // (in place: every residual element is read before it is written)
-          v[0] = v[0] + r0; v[1] = v[1] + r1; v[2] = v[2] + r2; v[3] = v[3] + r3;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = v[i];
-        if (MODE == 1 && out16) {
-          const uint32_t h01 = pack2h_hw(v[0], v[1]), h23 = pack2h_hw(v[2], v[3]);
-          uint16_t* o16 = out16 + (int64_t)b * ldo16 + n;
-          o16[0] = (uint16_t)(h01 & 0xffffu); o16[1] = (uint16_t)(h01 >> 16); o16[2] = (uint16_t)(h23 & 0xffffu); o16[3] = (uint16_t)(h23 >> 16);
-          if (h2_nonfinite(h01) | h2_nonfinite(h23)) atomicOr(flag, 1u);
-        }
-      } else {
-        uint16_t* o = reinterpret_cast<uint16_t*>(out) + (int64_t)b * ldo + n;
-        if (MODE == 1) {
-          const uint16_t* rr = reinterpret_cast<const uint16_t*>(res) + (int64_t)b * ldr + n;
-          const float r0 = bf2f(rr[0]), r1 = bf2f(rr[1]), r2 = bf2f(rr[2]), r3 = bf2f(rr[3]);   // (in place: read before written)
-          v[0] = round_bf(v[0]) + r0; v[1] = round_bf(v[1]) + r1; v[2] = round_bf(v[2]) + r2; v[3] = round_bf(v[3]) + r3;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = (uint16_t)f2bf(v[i]);
-      }
+      r = total(1 % NT);
+      o = (int64_t)b * ldo + n0 / 2 + q4;                     // pair p: gate row (p / 16) * 32 + p % 16, up row + 16
     }
+    if (MODE == 1) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r[i] = decode_epi_residual<F16>(res, (int64_t)b * ldr + n + i);
+    }
+    uint32_t ob = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ob |= decode_epi<MODE, F16>(v[i], r[i], out, o + i, out16, (int64_t)b * ldo16 + n + i);
+    if (F16 && ob) atomicOr(flag, 1u);
   }
 }
 
@@ -228,55 +199,38 @@ void dg_launch(const void* x, const void* W, void* out, const void* res, const v
 
 // the launch form depends on N (and the epilogue) only, never on B: 32 weight rows and 4 waves per workgroup for SWIGLU and for a STORE
 // at N >= 16384 with N % 32 == 0 (lm_head), else 16 rows and 8 waves (RESIDUAL always: the decoder's o_proj / down, N = hidden size)
-template <int MODE, bool PRENORM, bool F16>
-int dg_run(const char* name, const void* x, const void* W, void* out, const void* res, const void* ln_w, float eps, int B, int N, int K,
-           int64_t ldx, int64_t ldw, int64_t ldo, int64_t ldr, void* out16, int64_t ldo16, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  unsigned int* flag = F16 ? f16_flag_ptr() : nullptr;
-  GRIT_REQUIRE(!F16 || flag, GRIT_E_LAUNCH, "%s: the overflow flag word of this device is not reachable", name);
-  if constexpr (MODE == 2) {
-    dg_launch<MODE, PRENORM, F16, 2, 4>(x, W, out, res, ln_w, eps, B, N, K, ldx, ldw, ldo, ldr, flag, out16, ldo16, st);
-  } else if constexpr (MODE == 1) {
-    dg_launch<MODE, PRENORM, F16, 1, 8>(x, W, out, res, ln_w, eps, B, N, K, ldx, ldw, ldo, ldr, flag, out16, ldo16, st);
-  } else {
-    if (N >= 16384 && N % 32 == 0) dg_launch<MODE, PRENORM, F16, 2, 4>(x, W, out, res, ln_w, eps, B, N, K, ldx, ldw, ldo, ldr, flag, out16, ldo16, st);
-    else dg_launch<MODE, PRENORM, F16, 1, 8>(x, W, out, res, ln_w, eps, B, N, K, ldx, ldw, ldo, ldr, flag, out16, ldo16, st);
-  }
-  GRIT_CHECK_LAUNCH(name);
-  return GRIT_OK;
+template <int MODE, bool PRENORM, bool F16, class... Args>
+void dg_run(int N, Args... args) {
+  if constexpr (MODE == 2) dg_launch<MODE, PRENORM, F16, 2, 4>(args...);
+  else if constexpr (MODE == 1) dg_launch<MODE, PRENORM, F16, 1, 8>(args...);
+  else if (N >= 16384 && N % 32 == 0) dg_launch<MODE, PRENORM, F16, 2, 4>(args...);
+  else dg_launch<MODE, PRENORM, F16, 1, 8>(args...);
 }
 
-// STORE / SWIGLU with (pn) or without the deferred norm in front
-template <int MODE, bool F16, class... Args>
-int dg_run_norm(bool pn, Args... args) {
-  return pn ? dg_run<MODE, true, F16>(args...) : dg_run<MODE, false, F16>(args...);
-}
-
+// ln_w: the deferred norm in front (STORE / SWIGLU)
 template <bool F16>
 int dg_entry(const char* name, const void* x, const void* W, void* out, const void* ln_w, float eps, int B, int N, int K,
              int64_t ldx, int64_t ldw, int64_t ldo, int epilogue, const void* residual, int64_t ldr, void* out16, int64_t ldo16, void* stream) {
-  GRIT_REQUIRE(x && W && out, GRIT_E_BADARG, "%s: null pointer", name);
+  if (const int rc = decode_proj_pointers(name, x, W, out)) return rc;
   GRIT_REQUIRE(B >= 1 && B <= 64, GRIT_E_UNSUPPORTED, "%s: B=%d rows (1..64)", name, B);
   GRIT_REQUIRE(N > 0 && K > 0, GRIT_E_BADARG, "%s: bad sizes", name);
   GRIT_REQUIRE(K % 64 == 0, GRIT_E_UNSUPPORTED, "%s: K=%d must be a multiple of 64", name, K);
   GRIT_REQUIRE(N % 16 == 0, GRIT_E_UNSUPPORTED, "%s: N=%d must be a multiple of 16", name, N);
   GRIT_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= K && ldw >= K, GRIT_E_BADARG, "%s: bad leading dimensions", name);
-  GRIT_REQUIRE(aligned16(x) && aligned16(W) && (!ln_w || aligned16(ln_w)), GRIT_E_BADARG, "%s: pointers must be 16-byte aligned", name);
-  const bool pn = ln_w != nullptr;
-  switch (epilogue) {
-    case GRIT_EPI_STORE:
-      GRIT_REQUIRE(ldo >= N, GRIT_E_BADARG, "%s: ldo < N", name);
-      return dg_run_norm<0, F16>(pn, name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
-    case GRIT_EPI_RESIDUAL:
-      GRIT_REQUIRE(residual && ldo >= N && ldr >= N && !pn, GRIT_E_BADARG, "%s: RESIDUAL needs residual, ldo, ldr >= N (no pre-norm)", name);
-      GRIT_REQUIRE(!out16 || ldo16 >= N, GRIT_E_BADARG, "%s: ldo16 < N", name);
-      return dg_run<1, false, F16>(name, x, W, out, residual, nullptr, 0.f, B, N, K, ldx, ldw, ldo, ldr, out16, ldo16, stream);
-    case GRIT_EPI_SWIGLU:
-      GRIT_REQUIRE(N % 32 == 0 && ldo >= N / 2, GRIT_E_UNSUPPORTED, "%s: SWIGLU needs N %% 32 == 0, ldo >= N/2", name);
-      return dg_run_norm<2, F16>(pn, name, x, W, out, nullptr, ln_w, eps, B, N, K, ldx, ldw, ldo, 0, nullptr, 0, stream);
-    default: GRIT_REQUIRE(false, GRIT_E_BADARG, "%s: unknown epilogue %d", name, epilogue);
-  }
-  return GRIT_OK;
+  if (const int rc = decode_proj_aligned(name, x, W, ln_w)) return rc;
+  return decode_proj_epilogue(name, epilogue, ln_w != nullptr, N, ldo, residual, ldr, out16, ldo16, [&](auto mode) -> int {
+    constexpr int MODE = decltype(mode)::value;
+    unsigned int* flag;
+    if (const int rc = decode_proj_flag<F16>(name, &flag)) return rc;
+    auto run = [&](auto pn) {
+      dg_run<MODE, decltype(pn)::value, F16>(N, x, W, out, residual, ln_w, eps, B, N, K, ldx, ldw, ldo, ldr, flag, out16, ldo16, (hipStream_t)stream);
+    };
+    if constexpr (MODE == 1) run(std::false_type{});          // (RESIDUAL takes no norm: refused above)
+    else if (ln_w) run(std::true_type{});
+    else run(std::false_type{});
+    GRIT_CHECK_LAUNCH(name);
+    return GRIT_OK;
+  });
 }
 
 }  // namespace

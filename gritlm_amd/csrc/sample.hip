@@ -11,6 +11,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "next_token.h"
 
 namespace grit {
 namespace {
@@ -33,24 +34,11 @@ __device__ __forceinline__ uint32_t skey(float s) {
 // fixed-point softmax mass of a score: exp(s - M) in fp32, times 2^32, truncated (the maximum weighs exactly 2^32)
 __device__ __forceinline__ unsigned long long smass(float s, float M) { return (unsigned long long)(expf(s - M) * 4294967296.0f); }
 
+// the scaled scores of logits 8c .. 8c+7 (columns >= V: -inf, excluded)
 template <bool L32>
 __device__ __forceinline__ void load8(const void* row, int c, int V, float T, float (&s)[8]) {
   float x[8];
-  if (c * 8 + 8 <= V) {
-    if constexpr (L32) {
-      const float4 u = reinterpret_cast<const float4*>(row)[2 * c], w = reinterpret_cast<const float4*>(row)[2 * c + 1];
-      x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = w.x; x[5] = w.y; x[6] = w.z; x[7] = w.w;
-    } else {
-      const uint4 u = reinterpret_cast<const uint4*>(row)[c];
-      x[0] = bflo(u.x); x[1] = bfhi(u.x); x[2] = bflo(u.y); x[3] = bfhi(u.y); x[4] = bflo(u.z); x[5] = bfhi(u.z); x[6] = bflo(u.w); x[7] = bfhi(u.w);
-    }
-  } else {                                                     // the row's last, partial chunk: columns >= V are never read
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int v = c * 8 + e;
-      x[e] = v < V ? (L32 ? reinterpret_cast<const float*>(row)[v] : bf2f(reinterpret_cast<const uint16_t*>(row)[v])) : -INFINITY;
-    }
-  }
+  load8_logits<L32>(row, c, V, x);
 #pragma unroll
   for (int e = 0; e < 8; ++e) s[e] = scale_logit(x[e], T);
 }
@@ -230,36 +218,15 @@ __global__ void __launch_bounds__(ST) sample_advance_k(const void* __restrict__ 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int e = 4 * h + q;
-          if (skey(s[e]) >= lo) {
-            const float z = s[e] + gumbel(ctr[q]);
-            const int v = c * 8 + e;
-            if (z > bz || (z == bz && v < bi)) { bz = z; bi = v; }
-          }
+          if (skey(s[e]) >= lo) take_better(bz, bi, s[e] + gumbel(ctr[q]), c * 8 + e);
         }
       }
     });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float oz = __shfl_xor(bz, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (oz > bz || (oz == bz && oi < bi)) { bz = oz; bi = oi; }
-    }
-    if (lane == 0) { sm.wf[wave] = bz; sm.wi[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < SW; ++w)
-        if (sm.wf[w] > bz || (sm.wf[w] == bz && sm.wi[w] < bi)) { bz = sm.wf[w]; bi = sm.wi[w]; }
-      tok = bi;
-    }
+    block_best<SW>(bz, bi, sm.wf, sm.wi, tid);
+    tok = bi;                                                   // (thread 0's is the row's)
   }
-  if (tid == 0) {
-    next[b] = tok;
-    if (history) history[(int64_t)b * hist_stride + step[0]] = tok;
-    if (lens) lens[b] += 1;
-  }
+  if (tid == 0) commit_token(b, tok, next, lens, history, hist_stride, step);
 }
-
-__global__ void sample_bump_k(int32_t* v) { v[0] += 1; }
 
 }  // namespace
 }  // namespace grit
@@ -274,18 +241,11 @@ static int sample_launch(const char* name, const void* logits, int64_t ld, int V
   GRIT_REQUIRE(top_p >= 0.f && top_p <= 1.f, GRIT_E_BADARG, "%s: top_p must lie in [0, 1]", name);
   GRIT_REQUIRE(top_k >= 0, GRIT_E_BADARG, "%s: top_k must be >= 0", name);
   if (B == 0) return GRIT_OK;
-  GRIT_REQUIRE(logits && next && keys, GRIT_E_BADARG, "%s: null pointer", name);
-  GRIT_REQUIRE(V > 0 && ld >= V && ld % 8 == 0 && B > 0 && (!history || step), GRIT_E_BADARG, "%s: bad sizes", name);
-  GRIT_REQUIRE(aligned16(logits), GRIT_E_BADARG, "%s: logits must be 16-byte aligned", name);
+  if (const int rc = next_token_check(name, logits && next && keys, logits, ld, V, history, step, B)) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sample_advance_k<L32>, dim3((unsigned)B), dim3(ST), 0, st, logits, ld, V, next, lens, history, hist_stride, step,
                      temperature, top_k, top_p, (const unsigned long long*)keys);
-  GRIT_CHECK_LAUNCH(name);
-  if (step) {
-    hipLaunchKernelGGL(sample_bump_k, dim3(1), dim3(1), 0, st, step);
-    GRIT_CHECK_LAUNCH(name);
-  }
-  return GRIT_OK;
+  return next_token_finish(name, step, st);
 }
 
 extern "C" int grit_sample_advance(const void* logits, int64_t ld, int V, int64_t* next, int32_t* lens, int64_t* history, int64_t hist_stride,

@@ -148,12 +148,12 @@ class MistralDecoder:
         self.use_graph = True
         # which RMSNorms ride inside the following GEMV (grit_rmsnorm_gemv_bf16): "all" (input_layernorm -> q|k|v, post_attention_layernorm
         # -> gate|up, final norm -> lm_head), "qkv" (the MLP's and the final norm get their own launches) or "none"; GRIT_DECODE_FUSE_NORM for A/B runs
-        # (tools/decode_variants.sh).  Same bits in these three forms: the fused kernel applies the reference's two roundings.
+        # (profiles/r05_decode_variants.log).  Same bits in these three forms: the fused kernel applies the reference's two roundings.
         # "deferred" / "deferred_mlp": all three norms / the MLP's and the final one ride in the DEFERRED form (grit_rmsnorm_gemv_bf16_deferred:
         # the row scale multiplies the finished dot products, no second pass over the row; x_n is not rounded to bf16 -- one rounding fewer
         # than the reference's arithmetic).
         import os
-        # The exact forms (round 5, tools/decode_variants.sh on one box: all 3.49, qkv 3.25, none 3.32 ms per token): the 7168 workgroups of
+        # The exact forms (round 5, profiles/r05_decode_variants.log, one box: all 3.49, qkv 3.25, none 3.32 ms per token): the 7168 workgroups of
         # the gate|up GEMV -- and the 8000 of lm_head -- each re-derive the row's RMS when the norm is fused, which costs more than the
         # one-row launch it saves; the q|k|v GEMV is a single workgroup wave deep and keeps the fusion.
         # Default "deferred" (tools/decode_norm_ab.sh, one box: qkv 3.149, deferred_mlp 3.014, deferred 2.904, all 3.410 ms per token).

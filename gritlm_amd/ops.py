@@ -740,16 +740,12 @@ def attn_decode_rope(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, ca
     """rope_kv_append + attn_decode in one launch (qkv: the raw fused projection of the new token; the caches are appended to)."""
     B, _, Lmax, _ = cache_k.shape
     assert cos.shape[0] >= Lmax
-    if cache_k.dtype == F16:    # fp16-operand form: fp32 q|k|v row, fp16 caches and ctx
-        check(_lib.load().grit_attn_decode_rope_f16(_chk2d(qkv, F32, "qkv"), _chk(cos, F32, "cos"), _chk(sin, F32, "sin"), _chk(cache_k, F16, "cache_k"),
-                                                    _chk(cache_v, F16, "cache_v"), _chk(lens, I32, "lens"), _chk2d(out, F16, "out"),
-                                                    _chk(workspace, F32, "workspace"), B, nq, nkv, d, Lmax, qkv.stride(0), out.stride(0),
-                                                    float(d ** -0.5 if scale is None else scale), _stream()), "grit_attn_decode_rope_f16")
-        return out
-    check(_lib.load().grit_attn_decode_rope(_chk2d(qkv, BF16, "qkv"), _chk(cos, F32, "cos"), _chk(sin, F32, "sin"), _chk(cache_k, BF16, "cache_k"),
-                                            _chk(cache_v, BF16, "cache_v"), _chk(lens, I32, "lens"), _chk2d(out, BF16, "out"),
-                                            _chk(workspace, F32, "workspace"), B, nq, nkv, d, Lmax, qkv.stride(0), out.stride(0),
-                                            float(d ** -0.5 if scale is None else scale), _stream()), "grit_attn_decode_rope")
+    f16 = cache_k.dtype == F16  # fp16-operand form: fp32 q|k|v row, fp16 caches and ctx
+    fn, dt = (_lib.load().grit_attn_decode_rope_f16, F16) if f16 else (_lib.load().grit_attn_decode_rope, BF16)
+    check(fn(_chk2d(qkv, F32 if f16 else BF16, "qkv"), _chk(cos, F32, "cos"), _chk(sin, F32, "sin"), _chk(cache_k, dt, "cache_k"),
+             _chk(cache_v, dt, "cache_v"), _chk(lens, I32, "lens"), _chk2d(out, dt, "out"), _chk(workspace, F32, "workspace"), B, nq, nkv, d, Lmax,
+             qkv.stride(0), out.stride(0), float(d ** -0.5 if scale is None else scale), _stream()),
+          "grit_attn_decode_rope_f16" if f16 else "grit_attn_decode_rope")
     return out
 
 
@@ -818,16 +814,12 @@ def attn_prefill_cached(q: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.T
 def argmax_advance(logits: torch.Tensor, next_ids: torch.Tensor, lens: torch.Tensor | None = None, history: torch.Tensor | None = None,
                    step: torch.Tensor | None = None):
     B, V = logits.shape
-    if logits.dtype == F32:
-        check(_lib.load().grit_argmax_advance_f32(_chk2d(logits, F32, "logits"), logits.stride(0), V, _chk(next_ids, I64, "next"),
-                                                  0 if lens is None else _chk(lens, I32, "lens"), 0 if history is None else _chk(history, I64, "history"),
-                                                  0 if history is None else history.stride(0), 0 if step is None else _chk(step, I32, "step"), B,
-                                                  _stream()), "grit_argmax_advance_f32")
-        return next_ids
-    check(_lib.load().grit_argmax_advance(_chk2d(logits, BF16, "logits"), logits.stride(0), V, _chk(next_ids, I64, "next"),
-                                          0 if lens is None else _chk(lens, I32, "lens"), 0 if history is None else _chk(history, I64, "history"),
-                                          0 if history is None else history.stride(0), 0 if step is None else _chk(step, I32, "step"), B,
-                                          _stream()), "grit_argmax_advance")
+    f32 = logits.dtype == F32
+    fn = _lib.load().grit_argmax_advance_f32 if f32 else _lib.load().grit_argmax_advance
+    check(fn(_chk2d(logits, F32 if f32 else BF16, "logits"), logits.stride(0), V, _chk(next_ids, I64, "next"),
+             0 if lens is None else _chk(lens, I32, "lens"), 0 if history is None else _chk(history, I64, "history"),
+             0 if history is None else history.stride(0), 0 if step is None else _chk(step, I32, "step"), B, _stream()),
+          "grit_argmax_advance_f32" if f32 else "grit_argmax_advance")
     return next_ids
 
 

@@ -4671,6 +4671,9 @@ ALL_CHECKS = [
     ("decode_deferred_norm", check_decode_deferred_norm, {}),
     ("attn_decode", check_attn_decode, {}),
     ("attn_decode_gqa4_b1", check_attn_decode, dict(B=1, nq=32, nkv=8, Lmax=2304, lens=(2100,))),
+    ("attn_decode_mha", check_attn_decode, dict(B=2, nq=4, nkv=4, Lmax=512, lens=(300, 64))),                       # one head per group
+    ("attn_decode_gqa3", check_attn_decode, dict(B=2, nq=6, nkv=2, Lmax=256, lens=(63, 255))),                      # a group that is no power of two; a full and a nearly full first split
+    ("attn_decode_gqa8", check_attn_decode, dict(B=1, nq=16, nkv=2, Lmax=512, lens=(511,))),                        # the largest group; the last slot of the cache
     ("native_generate", check_native_generate, {}),
     ("native_generate_gqa", check_native_generate, dict(cfg_name="gqa", P=9, new=6, rows=3)),
     ("native_generate_exact_fused_norm", check_native_generate, dict(fuse_norm="all")),
@@ -4681,7 +4684,8 @@ ALL_CHECKS = [
     ("gemv_f16_7b", check_gemv_f16, dict(N=6144, K=4096)),
     ("attn_decode_f16", check_attn_decode_f16, {}),
     ("attn_decode_f16_gqa4_b1", check_attn_decode_f16, dict(B=1, nq=32, nkv=8, Lmax=2304, lens=(2100,))),
-    ("attn_decode_f16_mha", check_attn_decode_f16, dict(B=2, nq=4, nkv=4, Lmax=512, lens=(300, 64))),              # one query head per kv head: the non-per-head launch
+    ("attn_decode_f16_mha", check_attn_decode_f16, dict(B=2, nq=4, nkv=4, Lmax=512, lens=(300, 64))),              # one query head per kv head: the one-head-per-group case
+    ("attn_decode_f16_gqa3", check_attn_decode_f16, dict(B=2, nq=6, nkv=2, Lmax=256, lens=(63, 255))),
     ("attn_decode_f16_gqa8", check_attn_decode_f16, dict(B=1, nq=16, nkv=2, Lmax=512, lens=(511,))),               # 8 query heads per kv head; the last slot of the cache
     ("attn_decode_f16_long", check_attn_decode_f16, dict(B=1, nq=8, nkv=2, Lmax=8192, lens=(8000,))),              # 126 splits: the combine's tail loop beyond 64 splits
     ("argmax_f32", check_argmax_f32, {}),

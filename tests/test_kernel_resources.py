@@ -5,6 +5,7 @@ hand-placed LDS-DMA stream, and hipcc waits for them with ``s_waitcnt vmcnt(0)``
 GEMM's first K-tile drained the DMA queue once per tile and cost the K = 14336 launches the whole gain of the persistent form
 (NOTEBOOK.md §4, "what the compiler left in the persistent loop").  So: zero VGPR spills and zero scratch in every instantiation, and the
 occupancy the launch geometry counts on (two waves per SIMD)."""
+import functools
 import os
 import re
 import subprocess
@@ -15,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
+@functools.lru_cache(maxsize=None)          # one compilation per source file, shared by the tests that read it
 def _resources(src):
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(ROOT, "gritlm_amd", "csrc", src),
                         "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
@@ -52,6 +54,26 @@ def test_mfma_kernels_do_not_spill(src, needle, count, regs, waves):
     for k in ks:
         assert int(k["VGPRs Spill"]) == 0 and int(k["ScratchSize [bytes/lane]"]) == 0, k
         assert int(k["VGPRs"]) + int(k["AGPRs"]) <= regs and int(k["Occupancy [waves/SIMD]"]) >= waves, k
+
+
+# (source, kernel, instantiations, waves per SIMD at least): the token-by-token decode kernels
+_DECODE_KERNELS = [("decode.hip", "attn_decode_k", 4, 3), ("decode.hip", "gemv_bf16_k", 48, 2), ("decode.hip", "attn_decode_combine_k", 2, 3),
+                   ("sample.hip", "sample_advance_k", 2, 4)]
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@pytest.mark.parametrize("src,needle,count,waves", _DECODE_KERNELS, ids=["-".join(map(str, r[:3])) for r in _DECODE_KERNELS])
+def test_decode_kernels_do_not_spill(src, needle, count, waves):
+    """(counts: the decode attention is ONE form, a workgroup per query head -- {plain, RoPE + append} x {bf16, fp16 cache}; the GEMV's 12
+    forms -- bf16 {STORE, SWIGLU} x {no, exact, deferred norm} + RESIDUAL, fp16 {STORE, SWIGLU} x {no, deferred norm} + RESIDUAL -- x 1, 2,
+    4, 8 rows per launch; the combine and the sampler per format.)  These kernels are one workgroup wave deep and bound by their own
+    instruction streams: a scratch access in one of them is a memory round trip on the critical path of every decode step, and the
+    occupancy floors are what the instantiations had when the launch shapes were measured."""
+    ks = [k for k in _resources(src) if needle + "I" in k["name"]]
+    assert len(ks) == count, [k["name"] for k in ks]
+    for k in ks:
+        assert int(k["VGPRs Spill"]) == 0 and int(k["ScratchSize [bytes/lane]"]) == 0, k
+        assert int(k["Occupancy [waves/SIMD]"]) >= waves, k
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
