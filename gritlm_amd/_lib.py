@@ -120,6 +120,14 @@ _SIGNATURES = {
 }
 COMM_ID_BYTES = 128
 
+# include/gritlm_hip_index.h: the 16-bit index search, in a table (and a header) of its own until the call-trace recording that pins
+# _SIGNATURES is next re-made
+INDEX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gritlm_hip_index.h")
+_INDEX_SIGNATURES = {
+    "grit_knn16_workspace_bytes": (_l, [_i, _l, _i, _i]),
+    "grit_knn16_topk": (_i, [_p, _p, _i, _i, _l, _i, _l, _i, _p, _p, _p, _p]),
+}
+
 _lib = None
 
 
@@ -147,7 +155,7 @@ def load():
     # would fail with "no ROCm-capable device is detected" (found with build() followed by smoke() in one process): torch goes first.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_INDEX_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent -> loud
         fn.restype = res
         fn.argtypes = args

@@ -164,6 +164,14 @@ __device__ __forceinline__ void swiglu_bwd_elem(float d, float g, float u, float
   d_up = d * g * s;
 }
 
+// ---- top-k selection shared by the index searches (knn.hip, knn16.hip): "a before b" = higher score, lower index on equal scores;
+// topk_chunk_k (knn.hip) sorts chunks of TK_C candidates of a [Q, n] candidate list and keeps the k <= TK_C / 2 best of each.
+constexpr int TK_C = 2048;      // candidates per workgroup
+constexpr int TK_T = 256;
+__device__ __forceinline__ bool tk_before(float va, int64_t ia, float vb, int64_t ib) { return va > vb || (va == vb && ia < ib); }
+__global__ void topk_chunk_k(const float* __restrict__ vals, const int64_t* __restrict__ idx, int64_t n, int64_t ldv, int64_t ldi, int k,
+                             float* __restrict__ out_v, int64_t* __restrict__ out_i, int nchunks);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -8,11 +8,7 @@ namespace grit {
 int launch_f32_gemm_strided(const float* A, const float* B, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,
                             int64_t ldc, float alpha, hipStream_t st);   // infonce.hip
 
-constexpr int TK_C = 2048;      // candidates per workgroup
-constexpr int TK_T = 256;
-
-__device__ __forceinline__ bool tk_before(float va, int64_t ia, float vb, int64_t ib) { return va > vb || (va == vb && ia < ib); }
-
+// (TK_C candidates per workgroup, TK_T threads and the order tk_before: common.h, shared with knn16.hip)
 // vals [Q, n] (row stride ldv); idx (nullable) [Q, n]: candidate ids (implicit: position).  Workgroup (c, q) sorts candidates
 // [c*TK_C, (c+1)*TK_C) of row q and writes its best k to out_v/out_i [Q, nchunks, k].
 __global__ void __launch_bounds__(TK_T) topk_chunk_k(const float* __restrict__ vals, const int64_t* __restrict__ idx, int64_t n, int64_t ldv,

@@ -12,7 +12,17 @@ from typing import Optional
 
 import torch
 
-from . import ops
+from . import index_ops, ops
+
+_HALF_DTYPES = (torch.bfloat16, torch.float16)
+_ROW_PAD = 64        # elements: the row stride of a 16-bit GPU index built here, so that every row starts 16-byte aligned
+
+
+def _padded_index(dim: int, n: int, dtype, device):
+    """A zeroed [dim, n] view of a [dim, n rounded up to _ROW_PAD] allocation: shape, column fill and saving are those of a plain
+    matrix, and ``grit_knn16_topk`` stages its rows with single full-width loads."""
+    ld = max((n + _ROW_PAD - 1) // _ROW_PAD * _ROW_PAD, _ROW_PAD)
+    return torch.zeros((dim, ld), dtype=dtype, device=device)[:, :n]
 
 
 def _rank_world():
@@ -49,9 +59,14 @@ class DistributedIndex:
     ``search_knn`` / ``is_index_trained``.  Files are the reference's (``embeddings.<shard>.pt`` = ``torch.save`` of the [dim, n]
     column block, ``passages.<shard>.pt`` = pickled list of passage dicts): an index saved by either side loads on the other.
 
-    The scores of ``search_knn`` come from ``grit_knn_topk`` (exact-f32 MFMA similarity + chunked bitonic top-k; equal scores are
-    returned lower column first, where ``torch.topk`` promises nothing) on the [dim, N] layout as it lies.  The kernel computes in fp32: an
-    index of another ``dtype`` is widened for the search (the reference multiplies in the index dtype).
+    The scores of ``search_knn`` come from the native kernels on the [dim, N] layout as it lies; equal scores are returned lower column
+    first, where ``torch.topk`` promises nothing.  An fp32 index goes to ``grit_knn_topk`` (exact-f32 MFMA similarity + chunked bitonic
+    top-k).  A bf16 / fp16 index on the GPU goes to ``grit_knn16_topk``: searched in place with the top-k fused into the scan -- no fp32
+    copy, no [Q, N] score matrix -- against the fp32 queries split exactly into three 16-bit pieces, so only the fp32 accumulation
+    rounds (the reference multiplies in the index dtype).  ``init_embeddings`` and ``load_index`` give such an index a row stride that
+    is a multiple of 64 elements (``embeddings`` stays a [dim, N] view), which is the layout the kernel stages fastest; a tensor
+    assigned to ``embeddings`` directly is searched with whatever stride it has.  A 16-bit index on the host is widened to fp32 for
+    ``grit_knn_topk``.
 
     With an initialised process group every rank holds its shard of the passages (``load_passages`` deals them round-robin) and calls
     ``search_knn`` with ITS queries: the queries of all ranks are gathered, every rank searches its shard, and each rank receives the
@@ -68,7 +83,10 @@ class DistributedIndex:
     # ------------------------------------------------------------------ construction
     def init_embeddings(self, passages, dim: Optional[int]):
         self.doc_map = {i: doc for i, doc in enumerate(passages)}
-        self.embeddings = torch.zeros((dim, len(passages)), dtype=self.dtype, device="cuda" if self.is_in_gpu else "cpu")
+        if self.is_in_gpu and self.dtype in _HALF_DTYPES:
+            self.embeddings = _padded_index(dim, len(passages), self.dtype, "cuda")
+        else:
+            self.embeddings = torch.zeros((dim, len(passages)), dtype=self.dtype, device="cuda" if self.is_in_gpu else "cpu")
 
     # ------------------------------------------------------------------ persistence (the reference's shard files)
     @staticmethod
@@ -116,7 +134,16 @@ class DistributedIndex:
                 for p in pickle.load(f):
                     self.doc_map[len(self.doc_map)] = p
             e = torch.load(self._get_saved_embedding_path(path, shard), map_location="cpu")
-            blocks.append(e.cuda() if self.is_in_gpu else e)
+            blocks.append(e)
+        if self.is_in_gpu and blocks[0].dtype in _HALF_DTYPES:
+            self.embeddings = _padded_index(blocks[0].shape[0], sum(b.shape[1] for b in blocks), blocks[0].dtype, "cuda")
+            start = 0
+            for b in blocks:
+                self.embeddings[:, start:start + b.shape[1]] = b.cuda()
+                start += b.shape[1]
+            return
+        if self.is_in_gpu:
+            blocks = [b.cuda() for b in blocks]
         self.embeddings = blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
 
     # ------------------------------------------------------------------ search
@@ -124,8 +151,11 @@ class DistributedIndex:
         """index.py:97-104 (``queries @ embeddings`` -> ``torch.topk``) on the native kernel: scores [Q, topk] fp32 descending and
         the column of each.  ``topk`` larger than the shard returns the whole shard."""
         emb = self.embeddings
+        if emb.dtype in _HALF_DTYPES and emb.is_cuda:
+            q = allqueries.to(device=emb.device, dtype=torch.float32).contiguous()
+            return index_ops.knn16_topk(q, emb, min(topk, emb.shape[1]))
         if emb.dtype != torch.float32:
-            # the kernel takes fp32: widen a bf16 / fp16 index ONCE and keep the copy until the index tensor is replaced or written to
+            # a host index: grit_knn_topk takes fp32, widen ONCE and keep the copy until the index tensor is replaced or written to
             # (ADVICE r04: a fresh full-size copy per search_knn call tripled the footprint and re-read the whole index per query batch)
             key = (emb.data_ptr(), tuple(emb.shape), emb.dtype, emb._version)
             if getattr(self, "_emb32_key", None) != key:

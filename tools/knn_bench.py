@@ -1,26 +1,64 @@
 #!/usr/bin/env python3
-"""Index search timing: Q queries against N fp32 embeddings of width 4096 (rag/index.py:97-104).  python tools/knn_bench.py [--n 1000000]"""
+"""Index search timing: Q queries against N embeddings of width 4096 (rag/index.py:97-104).
+  python tools/knn_bench.py [--n 1000000] [--q 32] [--k 10] [--idxdtype float32|bfloat16|float16] [--ld-pad 0|1]
+float32: DenseIndex (grit_knn_topk) against torch's matmul + topk.  bfloat16 / float16: the index in the reference's [H, N] layout (row
+stride rounded up to 64 elements with --ld-pad 1, exactly N with 0), searched in one process, alternating, three repetitions each after
+a warm-up, by (a) the fp32 copy through ops.knn_topk in steady state -- the widening itself not counted -- and (b) grit_knn16_topk on the
+16-bit tensor as it lies.  One JSON line: both times, each one's bytes / 8 TB/s, the peak bytes each allocates, top-1 agreement."""
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from gritlm_amd import index_ops, ops  # noqa: E402
 from gritlm_amd.rag import DenseIndex  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=1000000); ap.add_argument("--q", type=int, default=32); ap.add_argument("--k", type=int, default=10)
+ap.add_argument("--idxdtype", choices=("float32", "bfloat16", "float16"), default="float32"); ap.add_argument("--ld-pad", type=int, choices=(0, 1), default=1)
 a = ap.parse_args()
-dev = "cuda"
-emb = torch.nn.functional.normalize(torch.randn((a.n, 4096), device=dev), dim=-1)
-idx = DenseIndex.from_rows(emb)
-q = torch.nn.functional.normalize(torch.randn((a.q, 4096), device=dev), dim=-1)
-s, i = idx.search_knn(q, a.k); torch.cuda.synchronize()
-t0 = time.perf_counter()
+dev, H = "cuda", 4096
+q = torch.nn.functional.normalize(torch.randn((a.q, H), device=dev), dim=-1)
+if a.idxdtype == "float32":
+    emb = torch.nn.functional.normalize(torch.randn((a.n, H), device=dev), dim=-1)
+    idx = DenseIndex.from_rows(emb)
+    s, i = idx.search_knn(q, a.k); torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(3):
+        s, i = idx.search_knn(q, a.k)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / 3
+    t0 = time.perf_counter()
+    for _ in range(3):
+        rs, ri = torch.topk(q @ emb.t(), a.k, dim=1)
+    torch.cuda.synchronize()
+    dt_ref = (time.perf_counter() - t0) / 3
+    print(json.dumps({"metric": "index search ms", "n_docs": a.n, "queries": a.q, "k": a.k, "ms": dt * 1e3, "embedding_gb": a.n * H * 4 / 1e9,
+                      "hbm_roofline_ms": a.n * H * 4 / 8e12 * 1e3, "torch_matmul_topk_ms": dt_ref * 1e3, "same_top1": float((i[:, 0] == ri[:, 0]).float().mean())}))
+    sys.exit(0)
+
+dt16 = torch.bfloat16 if a.idxdtype == "bfloat16" else torch.float16
+ld = (a.n + 63) // 64 * 64 if a.ld_pad else a.n
+e16 = torch.zeros((H, ld), dtype=dt16, device=dev)[:, :a.n]
+for c0 in range(0, a.n, 65536):                                   # unit-norm passages, written as column blocks (rag/eval.py:145)
+    blk = torch.nn.functional.normalize(torch.randn((min(65536, a.n - c0), H), device=dev), dim=-1)
+    e16[:, c0:c0 + blk.shape[0]] = blk.T.to(dt16)
+del blk
+e32 = e16.to(torch.float32)                                       # what the widened route keeps; its making is not timed
+routes = {"fp32_copy": lambda: ops.knn_topk(q, e32, a.k, transposed=True), "in_place": lambda: index_ops.knn16_topk(q, e16, a.k)}
+res, times, peak = {}, {r: [] for r in routes}, {}
+for r, fn in routes.items():                                      # warm-up, and the peak of what each route allocates
+    torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    res[r] = fn(); torch.cuda.synchronize()
+    peak[r] = torch.cuda.max_memory_allocated() - base
 for _ in range(3):
-    s, i = idx.search_knn(q, a.k)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / 3
-t0 = time.perf_counter()
-for _ in range(3):
-    rs, ri = torch.topk(q @ emb.t(), a.k, dim=1)
-torch.cuda.synchronize()
-dt_ref = (time.perf_counter() - t0) / 3
-print(json.dumps({"metric": "index search ms", "n_docs": a.n, "queries": a.q, "k": a.k, "ms": dt * 1e3, "embedding_gb": a.n * 4096 * 4 / 1e9,
-                  "hbm_roofline_ms": a.n * 4096 * 4 / 8e12 * 1e3, "torch_matmul_topk_ms": dt_ref * 1e3, "same_top1": float((i[:, 0] == ri[:, 0]).float().mean())}))
+    for r, fn in routes.items():
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record(); out = fn(); ev[1].record(); torch.cuda.synchronize()
+        times[r].append(ev[0].elapsed_time(ev[1]))
+ms = {r: sum(t) / len(t) for r, t in times.items()}
+bytes_ = {"fp32_copy": a.n * H * 4, "in_place": a.n * H * 2}
+print(json.dumps({"metric": "16-bit index search ms", "idxdtype": a.idxdtype, "n_docs": a.n, "queries": a.q, "k": a.k, "row_stride": ld,
+                  "fp32_copy_ms": ms["fp32_copy"], "in_place_ms": ms["in_place"], "fp32_copy_ms_all": times["fp32_copy"], "in_place_ms_all": times["in_place"],
+                  "fp32_copy_hbm_bound_ms": bytes_["fp32_copy"] / 8e12 * 1e3, "in_place_hbm_bound_ms": bytes_["in_place"] / 8e12 * 1e3,
+                  "in_place_fraction_of_hbm_bound": bytes_["in_place"] / 8e12 * 1e3 / ms["in_place"],
+                  "fp32_copy_peak_alloc_bytes": peak["fp32_copy"], "in_place_peak_alloc_bytes": peak["in_place"], "index_bytes": a.n * H * 2,
+                  "same_top1": float((res["fp32_copy"][1][:, 0] == res["in_place"][1][:, 0]).float().mean())}))
