@@ -128,6 +128,17 @@ _INDEX_SIGNATURES = {
     "grit_knn16_topk": (_i, [_p, _p, _i, _i, _l, _i, _l, _i, _p, _p, _p, _p]),
 }
 
+# include/gritlm_hip_prefix.h: decode attention over one shared copy of a prefix (prefix_ops.py), in a table of its own for the same reason
+PREFIX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gritlm_hip_prefix.h")
+_PREFIX_SIGNATURES = {
+    "grit_attn_decode_prefix_kc": (_i, []),
+    "grit_attn_decode_prefix_workspace_floats": (_l, [_i, _i, _i, _i, _i]),
+    "grit_rope_kv_append_tail": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _l, _l, _i, _p]),
+    "grit_attn_decode_prefix": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _l, _f, _i, _p]),
+    "grit_attn_decode_tail": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _l, _f, _i, _p]),
+    "grit_attn_decode_prefix_combine": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _l, _i, _p]),
+}
+
 _lib = None
 
 
@@ -155,7 +166,7 @@ def load():
     # would fail with "no ROCm-capable device is detected" (found with build() followed by smoke() in one process): torch goes first.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_INDEX_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_INDEX_SIGNATURES.items()) + list(_PREFIX_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent -> loud
         fn.restype = res
         fn.argtypes = args

@@ -27,7 +27,7 @@ import numbers
 
 import torch
 
-from . import ops
+from . import ops, prefix_ops
 from ._lib import EPI_RESIDUAL, EPI_STORE, EPI_SWIGLU
 from ._lib import GritHipError
 from .encoder import F16_POLICIES, MistralEncoderEngine, rope_tables
@@ -83,8 +83,9 @@ NORM_FORMS = {                  # q|k|v site, MLP and final sites
     "none":         (OWN,      OWN),
 }
 # attn: "rope" (grit_attn_decode_rope: RoPE + K/V append + attention in one launch, behind every fused q|k|v site), "append"
-# (grit_rope_kv_append + grit_attn_decode, behind a q|k|v norm with its own launch) or, for a prompt chunk, "rows" (grit_rope_kv_append_rows +
-# grit_attn_decode_rows over all rows).  groups: the row ranges (a, b) a projection runs over, [None] for the whole batch.
+# (grit_rope_kv_append + grit_attn_decode, behind a q|k|v norm with its own launch), for a prompt chunk "rows" (grit_rope_kv_append_rows +
+# grit_attn_decode_rows over all rows) or, for the n rows per sequence of share_prefix, "prefix" (the four launches of prefix_ops: every row
+# attends to its sequence's one prefix copy and to its own tail).  groups: the row ranges (a, b) a projection runs over, [None] for the whole batch.
 Plan = collections.namedtuple("Plan", "qkv_norm mlp_norm attn groups")
 
 
@@ -234,6 +235,13 @@ class MistralDecoder:
         elif plan.attn == "append":
             ops.rope_kv_append(qkv, cos, sin, ck, cv, lens, nq, nkv, d)
             ops.attn_decode(qkv, ck, cv, lens, ctx, ws, nq, nkv, d)
+        elif plan.attn == "prefix":                    # row v: prefix rows 0 .. plen[v // n] - 1 of its sequence, then its own tail (ck, cv)
+            n, plen, (pk, pv) = r["n"], r["plen"], r["prefix"][li]
+            Lpre, Ltail = pk.shape[2], ck.shape[2]
+            prefix_ops.rope_kv_append_tail(qkv, cos, sin, ck, cv, lens, plen, n, nq, nkv, d, q16=r["q16"])
+            prefix_ops.attn_decode_prefix(r["q16"] if r["f16"] else qkv, pk, pv, plen, ws, n, nq, nkv, d, Ltail)
+            prefix_ops.attn_decode_tail(qkv, ck, cv, lens, plen, ws, n, nq, nkv, d, Lpre)
+            prefix_ops.attn_decode_prefix_combine(ws, ctx, nq, nkv, d, Lpre, Ltail)
         else:                                          # "rows": row v is the token at position lens[v] of sequence rows[v]
             ops.rope_kv_append_rows(qkv, cos, sin, ck, cv, lens, r["rows"], nq, nkv, d)
             ops.attn_decode_rows(qkv, ck, cv, lens, r["rows"], ctx, ws, nq, nkv, d)
@@ -379,14 +387,39 @@ class MistralDecoder:
         else:
             ops.argmax_advance(st["logits"], st["next"], ln, st["history"], st["step"])
 
-    def _state(self, B: int, Lmax: int, f16: bool = False):
+    def _shared_state(self, st0, n: int, max_new_tokens: int):
+        """The decode state of share_prefix: B = B0 n rows on top of the B0-row state ``st0`` the prompt phase ran on.  Its cache stays
+        where it is -- rows 0 .. lens0[s] - 1 are sequence s's prefix, ONE copy -- and every row gets a tail cache [nkv, Ltail, d] for its
+        own tokens (Ltail: max_new_tokens rounded up to 64); lens [B] (global positions) start at lens0 repeated, plen [B0] = lens0 stays.
+        The first-step logits are st0's rows repeated n times consecutively (Hugging Face's order: row r = s n + j)."""
+        c, dev, f16 = self.cfg, self.device, st0["f16"]
+        nq, nkv, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        B0, Lpre = st0["lens"].shape[0], st0["cache"][0][0].shape[2]
+        B, Ltail = B0 * n, (max(max_new_tokens, 1) + 63) // 64 * 64
+        st = self._rows(B, f16)
+        cos, sin = rope_tables(Lpre + Ltail, d, c.rope_theta, self.eng.rope_bf16 and not f16, dev)
+        st.update(plan=st["plan"]._replace(attn="prefix"), n=n, prefix=st0["cache"], plen=st0["lens"].clone(), cos=cos, sin=sin,
+                  ws=prefix_ops.workspace(B, nq, nkv, Lpre, Ltail, dev), q16=torch.empty((B, nq * d), dtype=F16, device=dev) if f16 else None,
+                  cache=self._caches(B, Ltail, f16))
+        st["lens"].copy_(st0["lens"].repeat_interleave(n))
+        st["logits"].copy_(st0["logits"].repeat_interleave(n, dim=0))
+        if "cache_bad" in st0:
+            st["cache_bad"] = st0["cache_bad"]
+        return st
+
+    def _caches(self, B: int, L: int, f16: bool):
+        """per-layer (k, v) [B, nkv, L, d] in the operand format, zeroed"""
+        c, op = self.cfg, F16 if f16 else BF16
+        shape = (B, c.num_key_value_heads, L, c.head_dim)
+        return [(torch.zeros(shape, dtype=op, device=self.device), torch.zeros(shape, dtype=op, device=self.device)) for _ in range(c.num_hidden_layers)]
+
+    def _rows(self, B: int, f16: bool):
+        """The per-row buffers of a pass over B rows and its plan -- everything of a state that does not depend on a cache length."""
         c, dev = self.cfg, self.device
         nq, nkv, d = c.num_attention_heads, c.num_key_value_heads, c.head_dim
         op = F16 if f16 else BF16                      # operand rows and the K/V cache
         wide = F32 if f16 else BF16                    # the stream, the q|k|v row, the logits
         mk = lambda n, dt: torch.empty((B, n), dtype=dt, device=dev)
-        # (the fp16 policies rotate with the unrounded fp32 tables, like the encoder's fp16 forward)
-        cos, sin = rope_tables(Lmax, d, c.rope_theta, self.eng.rope_bf16 and not f16, dev)
         moe = {}
         if self.moe:
             moe = dict(act2=torch.empty((2 * B, c.intermediate_size), dtype=op, device=dev), y2=torch.empty((2 * B, c.hidden_size), dtype=wide, device=dev),
@@ -396,17 +429,21 @@ class MistralDecoder:
         # (xin: what a norm + projection launch reads of the stream -- its fp16 rounding under fp16 operands)
         return dict(**moe, f16=f16, plan=self._plan(B, f16), h=h, h16=h16, xin=h16 if f16 else h, x=mk(c.hidden_size, op), qkv=mk((nq + 2 * nkv) * d, wide), ctx=mk(nq * d, op),
                     act=mk(c.intermediate_size, op), logits=mk(self.lm_head.shape[0], wide), next=torch.zeros((B,), dtype=I64, device=dev),
-                    lens=torch.zeros((B,), dtype=I32, device=dev), step=torch.zeros((1,), dtype=I32, device=dev), cos=cos, sin=sin,
-                    ws=ops.attn_decode_workspace(B, nq, nkv, Lmax, dev),
-                    cache=[(torch.zeros((B, nkv, Lmax, d), dtype=op, device=dev), torch.zeros((B, nkv, Lmax, d), dtype=op, device=dev))
-                           for _ in range(c.num_hidden_layers)])
+                    lens=torch.zeros((B,), dtype=I32, device=dev), step=torch.zeros((1,), dtype=I32, device=dev))
+
+    def _state(self, B: int, Lmax: int, f16: bool = False):
+        c, dev = self.cfg, self.device
+        # (the fp16 policies rotate with the unrounded fp32 tables, like the encoder's fp16 forward)
+        cos, sin = rope_tables(Lmax, c.head_dim, c.rope_theta, self.eng.rope_bf16 and not f16, dev)
+        return dict(**self._rows(B, f16), cos=cos, sin=sin, ws=ops.attn_decode_workspace(B, c.num_attention_heads, c.num_key_value_heads, Lmax, dev),
+                    cache=self._caches(B, Lmax, f16))
 
     # ------------------------------------------------------------------ API
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int, attention_mask: torch.Tensor | None = None, past_key_values=None,
                  past_lens: torch.Tensor | None = None, eos_token_id: int | None = None, return_logits: bool = False,
                  on_overflow: str | None = None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
-                 seed: int | None = None, num_return_sequences: int = 1, _force_bf16: bool = False):
+                 seed: int | None = None, num_return_sequences: int = 1, share_prefix: bool = False, _force_bf16: bool = False):
         """Greedy (or, with ``do_sample``, sampled) continuation.  ``input_ids`` [B,P]: the NEW prompt tokens (right-padded rows need
         ``attention_mask``; with ``past_key_values`` all rows must be full length under ``prefill="rows"``, right-padded under ``"gemm"``).
         ``past_key_values``: per-layer K/V [B,nkv,S,d] of an already encoded prefix, e.g. the bidirectional document pass of ``encode(get_cache=True)``; ``past_lens`` [B] = valid prefix tokens per row
@@ -421,12 +458,24 @@ class MistralDecoder:
         ``top_p`` (1: off); defaults are GenerationConfig's -- by grit_sample_advance (semantics and RNG contract in include/gritlm_hip.h).
         Row r of the call draws with key ``seed + r`` (mod 2^64); ``seed=None`` takes one from torch's default CPU generator.
         ``num_return_sequences`` = n repeats every input row n times first (rows of one prompt consecutive, as ``repeat_interleave``), so
-        the call decodes B n rows and returns [B n, max_new_tokens].  The bf16 repeat of an fp16 overflow reuses the call's seed."""
+        the call decodes B n rows and returns [B n, max_new_tokens].  The bf16 repeat of an fp16 overflow reuses the call's seed.
+
+        ``share_prefix`` (with n > 1; a no-op at n = 1; dense engines only): everything before the first sampled token -- cached document
+        and prompt -- is computed once per input row and its K/V kept ONCE; the n rows of an input row attend to that shared prefix on the
+        MFMA (grit_attn_decode_prefix) and to a short tail of their own tokens, instead of to n copies of the cache.  Same row order, keys
+        and sampling; the prefix products round P (and, on fp16 operands, q) to the 16-bit operand format like the encoder's attention,
+        so the logits are not bit-identical to the expanded call's (both within the same bounds of the fp32 module).  Measured at the 7B shape
+        (tools/shared_prefix_bench.py, one box, B0 = 1): the shared step was the faster one at every measured point, prefix 256 included
+        (n = 20: 5.25 against 5.50 ms, n = 64: 8.10 against 9.56 ms) and 1.8x at prefix 2048, n = 64; shorter prefixes and smaller n
+        were not measured -- there the four attention launches per layer in place of two are the cost to weigh."""
         dev, c = self.device, self.cfg
         if self.prefill not in PREFILL_MODES:
             raise ValueError(f"MistralDecoder.prefill={self.prefill!r}: one of {PREFILL_MODES}")
         check_sampling(temperature, top_k, top_p, num_return_sequences, do_sample)
         n = int(num_return_sequences)
+        if share_prefix and self.moe:
+            raise NotImplementedError("native decode of a sparse-MoE (Mixtral) engine: share_prefix is built for dense engines")
+        shared = bool(share_prefix) and n > 1             # (n = 1: nothing to share, the plain path)
         attention_mask0, past_key_values0, past_lens0 = attention_mask, past_key_values, past_lens      # (the bf16 repeat expands again)
         B = input_ids.shape[0] * n
         if B > MAX_ROWS:
@@ -443,7 +492,7 @@ class MistralDecoder:
             ops.f16_overflow_flag(dev, clear=True)        # a stale flag of an earlier call is not this call's
             self.eng._f16_weights(self.eng.layers[0])     # (refuses weights beyond the fp16 range before anything runs)
         ids = input_ids.to(device=dev, dtype=I64)
-        if n > 1:                                         # Hugging Face's expansion: the n copies of a row are consecutive
+        if n > 1 and not shared:                          # Hugging Face's expansion: the n copies of a row are consecutive
             ids = ids.repeat_interleave(n, dim=0)
             attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(n, dim=0)
             past_lens = None if past_lens is None else past_lens.repeat_interleave(n, dim=0)
@@ -458,12 +507,9 @@ class MistralDecoder:
             # flash path slices it, modeling_mistral_gritlm.py:394-415) -- the decode kernels attend to the whole cache only
             raise NotImplementedError(f"native decode past the sliding window ({self.eng.window_keys} keys) is built for the sdpa semantics "
                                       "only (window_keys = 0: full causal attention over the cache)")
-        Lmax = (S0 + P + max_new_tokens + 255) // 256 * 256
+        # (share_prefix: the prompt phase runs on the B0 un-expanded rows, on a state whose cache ends with the prompt)
+        Lmax = (S0 + P + (0 if shared else max_new_tokens) + 255) // 256 * 256
         st = self._state(B, Lmax, f16)
-        st["history"] = torch.zeros((B, max_new_tokens), dtype=I64, device=dev)
-        if do_sample:
-            st["sampling"], st["keys"] = (float(temperature), int(top_k), float(top_p)), row_keys(seed, B, dev)
-        logits_all = torch.empty((B, max_new_tokens, self.lm_head.shape[0]), dtype=st["logits"].dtype, device=dev) if return_logits else None
         if past is None:
             # prefill: one causal pass over the prompt that also emits the post-RoPE K/V (the encoder engine's forward)
             mask = torch.ones((B, P), dtype=I64, device=dev) if attention_mask is None else attention_mask.to(device=dev, dtype=I64)
@@ -501,6 +547,13 @@ class MistralDecoder:
                     self._step(st)
                     st["lens"] += 1
                 self.last_prefill = "tokens"
+        if shared:                                        # the decode phase: B0 n rows on the one prefix copy and their own tails
+            st = self._shared_state(st, n, max_new_tokens)
+            B *= n
+        st["history"] = torch.zeros((B, max_new_tokens), dtype=I64, device=dev)
+        if do_sample:
+            st["sampling"], st["keys"] = (float(temperature), int(top_k), float(top_p)), row_keys(seed, B, dev)
+        logits_all = torch.empty((B, max_new_tokens, self.lm_head.shape[0]), dtype=st["logits"].dtype, device=dev) if return_logits else None
         # first generated token from the prefill logits, then decode steps (graph replay)
         if return_logits:
             logits_all[:, 0].copy_(st["logits"])
@@ -530,7 +583,8 @@ class MistralDecoder:
             if on_overflow == "bf16":
                 return self.generate(input_ids, max_new_tokens, attention_mask=attention_mask0, past_key_values=past_key_values0,
                                      past_lens=past_lens0, eos_token_id=eos_token_id, return_logits=return_logits, do_sample=do_sample,
-                                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, num_return_sequences=n, _force_bf16=True)
+                                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, num_return_sequences=n, share_prefix=share_prefix,
+                                     _force_bf16=True)
             raise GritHipError("native decode on fp16 operands: a value exceeded the fp16 range (activation, K/V or a cached K/V that was "
                                "already inf); the tokens of this call are invalid -- decode with precision 'bf16' (MistralDecoder.precision, "
                                "or on_overflow='bf16')")

@@ -313,16 +313,18 @@ class GritLM(torch.nn.Module):
     @torch.no_grad()
     def sample_native(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None, past_key_values=None, max_new_tokens: int = 16,
                       min_new_tokens: int = 0, pad_token_id: int | None = None, eos_token_id: int | None = None, temperature: float = 1.0,
-                      top_k: int = 50, top_p: float = 1.0, num_return_sequences: int = 1, seed: int | None = None) -> torch.Tensor:
+                      top_k: int = 50, top_p: float = 1.0, num_return_sequences: int = 1, seed: int | None = None,
+                      share_prefix: bool = False) -> torch.Tensor:
         """``model.generate(..., do_sample=True, temperature=, top_k=, top_p=, num_return_sequences=)`` on the native decoder: the call of
         ``generate_native`` with every token drawn on the device (MistralDecoder.generate(do_sample=True): Hugging Face's temperature ->
         top-k -> top-p warpers, then a Gumbel-max draw on Philox noise keyed by ``seed`` + row).  Returns [B n, P + new] like Hugging Face's
         ``generate``: every input row repeated n times (consecutively), then its new tokens, pad after a row's EOS, the common tail trimmed.
         ``seed=None`` draws the seed from torch's default CPU generator, so ``torch.manual_seed`` / ``transformers.set_seed`` reproduce a
-        call; the tokens are not those of ``torch.multinomial`` (another RNG)."""
+        call; the tokens are not those of ``torch.multinomial`` (another RNG).  ``share_prefix``: the n rows of an input row attend to ONE
+        copy of its cached document + prompt K/V instead of n (MistralDecoder.generate)."""
         return self._native_call(input_ids, attention_mask, past_key_values, max_new_tokens, min_new_tokens, pad_token_id, eos_token_id,
                                  dict(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                                      num_return_sequences=num_return_sequences))
+                                      num_return_sequences=num_return_sequences, share_prefix=share_prefix))
 
     def _native_call(self, input_ids, attention_mask, past_key_values, max_new_tokens, min_new_tokens, pad_token_id, eos_token_id,
                      sampling: dict | None = None) -> torch.Tensor:
